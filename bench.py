@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Training-step throughput of the voxel-SR hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 One "step" = forward + loss + zero_grad + backward (+ gradient all-reduce for
 N > 1) + Adam of the reference's UNetSR (default.yml widths, 65.47 M parameters)
@@ -9,16 +9,24 @@ on one synthetic batch, i.e. the body of reference
 pytorch/src/optim_helper.py:156-178.
 
 Workload (HR 80x320x320 from LR 20x80x80, fp32, weak scaling):
-  N = 1 : BASELINE.json configs[1] -- batch 1, L1 loss.  A short second measurement of configs[2] (batch 4, the
-          physics-guided loss: the per-GPU work of configs[3]) is attached as "config2_batch4_mixed".
+  N = 1 : BASELINE.json configs[1] -- batch 1, L1 loss.  With --full a short second measurement of configs[2] (batch 4,
+          the physics-guided loss: the per-GPU work of configs[3]) is attached as "config2_batch4_mixed".
   N > 1 : BASELINE.json configs[3] -- batch 4 per GPU (global 4 N), physics-guided loss, gradient all-reduce over
-          RCCL.  A short second measurement of configs[1]'s per-GPU work (batch 1, L1) is attached as
+          RCCL.  With --full a short second measurement of configs[1]'s per-GPU work (batch 1, L1) is attached as
           "config1_batch1_l1", so that per-GPU throughput can be compared with the N = 1 line like for like.
 ``--batch`` / ``--loss`` override the primary workload.
 
-Prints ONE JSON line (rank 0) with the metric, the roofline figure of the
-dominant kernel measured live with HIP events, GB/s of the HBM-bound kernel families,
-and a CPU baseline (the oracle, timed on this host's cores on a bounded sample).
+Prints ONE JSON line (rank 0) with the metric, ms_per_step of the K timed steps and the roofline figure of the
+dominant kernel, measured live with HIP events inside the timed steps.  A plain run does nothing else.  --full adds
+what takes runs of its own: the per-family kernel breakdown (GB/s of the HBM-bound kernel families) from untimed
+steps, the attached workloads (second configuration, fp32-MFMA-only, bf16 storage, hipGraph replay) and a CPU
+baseline (the oracle, timed on this host's cores on a bounded sample).
+
+--dump-outputs DIR writes what the last timed step computed, as float32 .npy files: loss, pred (the model's output;
+not with --graph, whose captured step keeps it inside the graph), params (the parameters after the Adam update) and
+grads (the parameter gradients it applied).  An array of more than DUMP_SAMPLE elements is written as a fixed, seeded
+sample of DUMP_SAMPLE of its elements (flat indices, the same for every run of the same arguments).  Inputs and
+initial weights are seeded, so two builds can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -49,6 +57,7 @@ HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 
 BYTES_PER_VOXEL = 11_586       # compulsory fwd+bwd activation traffic per HR voxel, fp32
 FAMILIES = {"igemm_s1": 0, "igemm_s2": 1, "igemm_bwd_s2": 2, "wgrad": 3, "loss": 4, "act_bwd": 5, "bias_grad": 6,
             "adam": 7, "data": 8, "pack_reduce": 9, "hconv": 11, "hconv_small": 12}
+DUMP_SAMPLE = 1 << 22          # --dump-outputs: elements per array at most (16 MB of float32; 3 large arrays + the loss)
 
 DEFAULT_CONFIG = {
     "data": {"stds": [8.40, 14.40, 21.60, 7.00]},
@@ -130,6 +139,16 @@ def cpu_baseline(cfg, budget_s=20.0):
                       f"80x320x320 volume of the GPU workload needs ~35 GB and minutes per step on CPU"}
 
 
+def dump_array(t, seed):
+    """a tensor as a flat float32 array: whole, or DUMP_SAMPLE elements at seeded (sorted) flat indices"""
+    flat = t.detach().reshape(-1)
+    if flat.numel() > DUMP_SAMPLE:
+        g = torch.Generator().manual_seed(seed)
+        idx = torch.randint(flat.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+        flat = flat[idx.to(flat.device)]
+    return flat.to(device="cpu", dtype=torch.float32, copy=True).numpy()
+
+
 def read_profile(L):
     prof = {}
     for name, kid in list(FAMILIES.items()) + [("dropped", 99)]:
@@ -140,11 +159,12 @@ def read_profile(L):
 
 
 def measure(sr3d_amd, L, dev, rank, world, use_dist, batch, loss_name, lr_grid, steps, warmup, graph=False, breakdown_steps=0,
-            storage="fp32"):
+            storage="fp32", dump=False):
     """W untimed + K timed training steps of one workload; returns wall time (max over ranks), the HIP-event totals of
     the dominant (stride-1 convolution) kernel family inside the timed steps, and -- from `breakdown_steps` further,
     UNTIMED steps -- the totals of every family.  (Inside the timed region only the dominant family is bracketed: 48
-    instead of ~1100 event records per step; measured cost of bracketing everything: 0.3-0.7 % of the step.)"""
+    instead of ~1100 event records per step; measured cost of bracketing everything: 0.3-0.7 % of the step.)
+    dump: also return what the last timed step computed (see --dump-outputs) as numpy arrays under "outputs"."""
     import gc
     gc.collect()              # a previous leg's hipGraph (and its private memory pool) dies with its last reference
     if torch.device(dev).type == "cuda":
@@ -166,6 +186,8 @@ def measure(sr3d_amd, L, dev, rank, world, use_dist, batch, loss_name, lr_grid, 
     if torch.device(dev).type == "cuda":
         torch.cuda.reset_peak_memory_stats(dev)
 
+    capture = {"on": False, "pred": None}   # the last timed step keeps its prediction when outputs are dumped
+
     def step():
         pred = model(x, b)
         loss = loss_fn(pred, y, b)
@@ -174,6 +196,8 @@ def measure(sr3d_amd, L, dev, rank, world, use_dist, batch, loss_name, lr_grid, 
         if reducer is not None:
             opt.grad_scale = reducer.finish()
         opt.step()
+        if capture["on"]:
+            capture["pred"] = pred.detach()
         return loss
 
     if graph:      # the whole step captured once into a hipGraph; every step below is one replay (+ with N > 1 the bucket
@@ -207,13 +231,21 @@ def measure(sr3d_amd, L, dev, rank, world, use_dist, batch, loss_name, lr_grid, 
         L.profile_enable(int(os.environ.get("SR3D_BENCH_PROFILE_MODE", "2")))
     fence()
     t0 = time.perf_counter()
-    for _ in range(steps):
+    for i in range(steps):
+        capture["on"] = dump and i == steps - 1
         loss = step()
         keep(loss)
     fence()
     elapsed = time.perf_counter() - t0
     last_loss = float(loss.detach())
     losses = [float(v) for v in losses]
+    outputs = None
+    if dump:                            # before the breakdown steps move the parameters on
+        outputs = {"loss": dump_array(loss, 0), "params": dump_array(opt.flat_param, 2),
+                   "grads": dump_array(opt.flat_grad, 3)}
+        if capture["pred"] is not None:
+            outputs["pred"] = dump_array(capture["pred"], 1)
+        capture["pred"] = None
 
     prof = read_profile(L)              # dominant family, timed steps
     L.profile_enable(False)
@@ -236,7 +268,7 @@ def measure(sr3d_amd, L, dev, rank, world, use_dist, batch, loss_name, lr_grid, 
         torch.cuda.empty_cache()
     return {"elapsed": float(t.item()), "prof": prof, "breakdown": breakdown, "breakdown_steps": breakdown_steps,
             "loss": last_loss, "losses": losses, "hr": hr, "cfg": cfg, "peak_mem_gb": (torch.cuda.max_memory_allocated(dev) / 2 ** 30 if on_gpu else 0.0),
-            "voxels_per_step": world * batch * hr[0] * hr[1] * hr[2]}
+            "voxels_per_step": world * batch * hr[0] * hr[1] * hr[2], "outputs": outputs}
 
 
 def workload_name(lr_grid, hr, batch, loss_name, world, storage="fp32"):
@@ -267,7 +299,14 @@ def main():
                     help="capture the training step into a hipGraph and time replays (no per-kernel breakdown)")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise RCCL and the bucketed all-reduce even with one rank (rehearsal of the N>1 path)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the kernel breakdown, the attached workloads and the CPU baseline (runs of their own; "
+                         "--no-secondary / --no-cpu-baseline drop parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -291,7 +330,14 @@ def main():
     batch = args.batch if args.batch is not None else (1 if world == 1 else 4)
     loss_name = args.loss if args.loss is not None else ("l1" if world == 1 else "mixed")
     m = measure(sr3d_amd, L, dev, rank, world, use_dist, batch, loss_name, args.lr_grid, args.steps, args.warmup,
-                graph=args.graph, breakdown_steps=0 if args.graph else 2, storage=args.storage)
+                graph=args.graph, breakdown_steps=2 if args.full and not args.graph else 0, storage=args.storage,
+                dump=args.dump_outputs is not None and rank == 0)
+    if m["outputs"] is not None:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in m["outputs"].items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+    secondary = args.full and not args.no_secondary   # every leg below is a run of its own: --full only
     leg_errors = {}
 
     def attached(name, fn):
@@ -309,7 +355,7 @@ def main():
             return None
 
     second = None
-    if not args.no_secondary and args.batch is None and args.loss is None and not args.graph:
+    if secondary and args.batch is None and args.loss is None and not args.graph:
         sb, sl = (4, "mixed") if world == 1 else (1, "l1")
         second = attached("second", lambda: measure(sr3d_amd, L, dev, rank, world, use_dist, sb, sl, args.lr_grid,
                                                     min(args.steps, 3), 1, breakdown_steps=1))
@@ -317,7 +363,7 @@ def main():
             second["batch"], second["loss_name"] = sb, sl
 
     fp32_only = None   # the same configuration with every stride-1 layer back on the fp32 Winograd kernel
-    if not args.no_secondary and not args.graph and os.environ.get("SR3D_SPLIT_F16", "1") != "0":
+    if secondary and not args.graph and os.environ.get("SR3D_SPLIT_F16", "1") != "0":
         prev = os.environ.get("SR3D_SPLIT_F16")
         os.environ["SR3D_SPLIT_F16"] = "0"
         fp32_only = attached("fp32_mfma_only", lambda: measure(sr3d_amd, L, dev, rank, world, use_dist, batch, loss_name,
@@ -331,14 +377,14 @@ def main():
     # like for like with the fp32 line above; (b) configs[4]'s per-GPU workload: LR 40x160x160 -> HR 160x640x640, batch 1,
     # physics-guided loss, the whole step captured into a hipGraph and replayed
     bf16_same, bf16_c4 = None, None
-    if not args.no_secondary and not args.graph and not use_dist and os.environ.get("SR3D_BENCH_BF16", "1") != "0":
+    if secondary and not args.graph and not use_dist and os.environ.get("SR3D_BENCH_BF16", "1") != "0":
         bf16_same = attached("bf16_storage", lambda: measure(sr3d_amd, L, dev, rank, world, use_dist, batch, loss_name, args.lr_grid,
                                                              min(args.steps, 5), 1, breakdown_steps=1, storage="bf16"))
         bf16_c4 = attached("config4_bf16_hipgraph", lambda: measure(sr3d_amd, L, dev, rank, world, use_dist, 1, "mixed", [40, 160, 160],
                                                                     min(args.steps, 3), 1, graph=True, storage="bf16"))
 
     replay = None      # the same step captured once into a hipGraph and replayed (src/graph.py): no per-launch overhead
-    if not args.no_secondary and not args.graph and not use_dist:
+    if secondary and not args.graph and not use_dist:
         replay = attached("hipgraph_replay", lambda: measure(sr3d_amd, L, dev, rank, world, use_dist, batch, loss_name, args.lr_grid,
                                                              min(args.steps, 5), 2, graph=True))
 
@@ -430,13 +476,14 @@ def main():
                         "contraction-bound (AI ~ 730 FLOP/B), so this fraction cannot exceed ~1/16 at fp32-MFMA peak "
                         "even with Winograd",
             "step_algorithmic_tflops": FLOP_PER_VOXEL * value / 1e12,
-            "conv_kernels": conv,
-            "hbm_bound_kernels": hbm,
-            "kernel_breakdown_note": ("conv_kernels / hbm_bound_kernels come from 2 further, UNTIMED steps with every launch "
-                                      "bracketed by HIP events; inside the timed region only the roofline kernel family is"),
             "profile_records_dropped": prof["dropped"]["launches"] + (m["breakdown"]["dropped"]["launches"] if m["breakdown"] else 0),
             "loss": m["loss"],
         }
+        if args.full:
+            out["conv_kernels"], out["hbm_bound_kernels"] = conv, hbm
+            out["kernel_breakdown_note"] = ("conv_kernels / hbm_bound_kernels come from 2 further, UNTIMED steps with every "
+                                            "launch bracketed by HIP events; inside the timed region only the roofline kernel "
+                                            "family is")
         if second is not None:
             key = "config2_batch4_mixed" if world == 1 else "config1_batch1_l1"
             sv = second["voxels_per_step"] * min(args.steps, 3) / second["elapsed"]
@@ -502,7 +549,7 @@ def main():
                 "value": bf16_c4["voxels_per_step"] * n3 / bf16_c4["elapsed"], "unit": "HR voxels/s", "steps": n3, "warmup": 1,
                 "ms_per_step": bf16_c4["elapsed"] / n3 * 1e3, "loss": bf16_c4["loss"], "peak_mem_gb": bf16_c4["peak_mem_gb"],
                 "step_algorithmic_tflops": FLOP_PER_VOXEL * bf16_c4["voxels_per_step"] * n3 / bf16_c4["elapsed"] / 1e12}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(m["cfg"])
         print(json.dumps(out), flush=True)
 

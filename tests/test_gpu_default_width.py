@@ -254,15 +254,16 @@ def test_fullwidth_layer_fwd_dgrad_wgrad(eng, name, cin, cout, stride, grid, gat
 
 def test_193_gradient_rows_on_a_large_grid(eng):
     """up1.convs.0's input gradient: 64 + 129 = 193 rows (the mask slice in the middle needs none) on a grid with
-    more than 500k voxels, where the 193rd row leaves the MFMA tiles for the small-N kernel"""
+    more than 500k voxels, where the 193rd row leaves the MFMA tiles for the small-N kernel.  The oracle runs in fp64: an
+    fp32 CPU weight gradient over 500k voxels is itself ~1e-5 off, by how many threads split its reduction"""
     g = torch.Generator().manual_seed(193)
     grid = (16, 128, 256)
     cin, cout = 194, 64
     x = torch.rand(1, cin, *grid, generator=g) - 0.5
     w = torch.randn(cout, cin, 3, 3, 3, generator=g) * (2.0 / (27 * cin)) ** 0.5
     gy = torch.rand(1, cout, *grid, generator=g) - 0.5
-    xr, wr = x.clone().requires_grad_(True), w.clone().requires_grad_(True)
-    F.conv3d(xr, wr, None, padding=1).backward(gy)
+    xr, wr = x.double().requires_grad_(True), w.double().requires_grad_(True)
+    F.conv3d(xr, wr, None, padding=1).backward(gy.double())
     parts = [x[:, :64].contiguous().to(DEV).requires_grad_(True), x[:, 64:65].contiguous().to(DEV),
              x[:, 65:].contiguous().to(DEV).requires_grad_(True)]
     wd = w.to(DEV).requires_grad_(True)

@@ -6,7 +6,7 @@ TAG=${1:-r02}
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-B="python3 bench.py --no-cpu-baseline --no-secondary"
+B="python3 bench.py --full --no-cpu-baseline --no-secondary"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_config1 -o c1 -- $B --steps 3 --warmup 1 > $OUT/stats_config1.log 2>&1 || exit 1
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_config2 -o c2 -- $B --steps 2 --warmup 1 --batch 4 --loss mixed > $OUT/stats_config2.log 2>&1 || exit 1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o f -- $B --steps 1 --warmup 1 > $OUT/pmc_fetch.log 2>&1 || exit 1

@@ -5,7 +5,7 @@ TAG=$1; shift
 OUT=gpurun_out/stats_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/t -o s -- python3 bench.py --no-cpu-baseline --no-secondary --steps 3 --warmup 1 "$@" > $OUT/log.txt 2>&1 || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/t -o s -- python3 bench.py --full --no-cpu-baseline --no-secondary --steps 3 --warmup 1 "$@" > $OUT/log.txt 2>&1 || exit 1
 find $OUT/t -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats.csv \;
 rm -rf $OUT/t
 python3 - <<PY

@@ -6,7 +6,7 @@ TAG=$1
 OUT=gpurun_out/trace_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $OUT/t -o k -- python3 bench.py --no-cpu-baseline --no-secondary --steps 1 --warmup 1 > $OUT/log.txt 2>&1 || exit 1
+rocprofv3 --kernel-trace --output-format csv -d $OUT/t -o k -- python3 bench.py --full --no-cpu-baseline --no-secondary --steps 1 --warmup 1 > $OUT/log.txt 2>&1 || exit 1
 python3 - <<PY
 import csv,glob
 f=glob.glob("$OUT/t/**/*kernel_trace.csv", recursive=True)[0]
