@@ -29,6 +29,7 @@ EVAL_INDEX = {"L1": 0, "L2": 1, "MaskedL1": 2, "MaskedL2": 3, "MaskedL1NearWall"
               "AbsDiffTemperatureLev": 10, "DiffVelocityNormLev": 11, "AbsDiffDivergence": 12, "DiffOmegaNorm": 13}
 EVAL_SUMS = {"abs": 14, "mask_abs": 15, "sq": 16, "mask_sq": 17, "mask": 18}
 EVAL_COUNT = 19
+ROTATE_COEF_READY, ROTATE_PHYSICAL = 1, 2   # flags of the rotation calls (include/sr3d.h: SR3D_ROTATE_*)
 
 
 class Slice(C.Structure):
@@ -77,6 +78,11 @@ SYMBOLS = {
     "sr3d_weighted_lp_bwd": (_I, [_P, _P, _P, _I, _I, _LL, _I, _P, _P, _P]),
     "sr3d_eval_metrics_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
     "sr3d_eval_metrics": (_I, [_P, _P, _P, _I, _I, _I, _I, C.POINTER(_F), _F, _I, _P, _P, _P]),
+    "sr3d_rotate_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I]),
+    "sr3d_rotate_fields": (_I, [_P, _P, _I, _I, _I, _I, _I, C.POINTER(_D), C.POINTER(_D), _D, _I, _P, _SZ, _P]),
+    "sr3d_rotate_building": (_I, [_P, _P, _I, _I, _I, _I, _I, _D, _D, _I, _P, _SZ, _P]),
+    "sr3d_equivariance_errors": (_I, [_P, _P, _I, _I, _I, _I, C.POINTER(_D), C.POINTER(_D), _D, _I, _I, _I, _I, _I, _P,
+                                      _P, _SZ, _P]),
     "sr3d_ssim3d_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I]),
     "sr3d_ssim3d": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, C.POINTER(_F), _I, _F, _F, _P, _P, _P, _P]),
     "sr3d_adam_step": (_I, [_P, _P, _P, _P, _LL, _D, _D, _D, _D, _I, _D, _P]),

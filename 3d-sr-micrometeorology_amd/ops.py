@@ -596,6 +596,94 @@ def ssim3d(img1: torch.Tensor, img2: torch.Tensor, mask: torch.Tensor, window: S
     return mean[0] if size_average else smap
 
 
+# ---------------------------------------------------------------- rotation about z (equivariance evaluation)
+def rotate_workspace(t: torch.Tensor) -> torch.Tensor:
+    """a workspace for the rotation calls on a tensor of t's shape (include/sr3d.h: sr3d_rotate_workspace_bytes);
+    after a call it holds t's spline coefficients, which ``coef_ready=True`` reuses at another angle"""
+    if not t.is_cuda:
+        raise RuntimeError("rotate_workspace: the tensor must live on the GPU: the sr3d engine has no CPU path")
+    if t.dim() != 5:
+        raise ValueError("rotate_workspace expects a (B, C, Z, Y, X) tensor")
+    return torch.empty(L.lib.sr3d_rotate_workspace_bytes(*[int(v) for v in t.shape]), dtype=torch.uint8,
+                       device=t.device)
+
+
+def _ws_ptr(ws: Optional[torch.Tensor], t: torch.Tensor, coef_ready: bool):
+    if ws is None:
+        if coef_ready:
+            raise ValueError("coef_ready=True needs the workspace of the earlier call")
+        ws = rotate_workspace(t)
+    if not ws.is_cuda:
+        raise RuntimeError("the rotation workspace must live on the GPU")
+    return ws, C.c_void_p(ws.data_ptr()), ws.numel() * ws.element_size()
+
+
+def _rot_input(t: torch.Tensor, what: str) -> torch.Tensor:
+    if not t.is_cuda:
+        raise RuntimeError(f"{what} must live on the GPU: the sr3d engine has no CPU path")
+    if t.dim() != 5:
+        raise ValueError(f"{what} must be (B, C, Z, Y, X)")
+    return t.detach().contiguous()
+
+
+def _scales(means: Sequence[float], scales: Sequence[float]):
+    if len(means) != 4 or len(scales) != 4:
+        raise ValueError("means and scales have one entry per channel (T, u, v, w)")
+    return (C.c_double * 4)(*[float(v) for v in means]), (C.c_double * 4)(*[float(v) for v in scales])
+
+
+def rotate_fields(x: torch.Tensor, means: Sequence[float], scales: Sequence[float], angle: float,
+                  rescaled: bool = True, workspace: Optional[torch.Tensor] = None,
+                  coef_ready: bool = False) -> torch.Tensor:
+    """rotate_temperature_velocity of the reference (src/equivariance_error_calculator.py:6-46) on the GPU: every
+    (y, x) plane of the normalised (B, 4, Z, Y, X) fields rotated by ``angle`` degrees as scipy.ndimage.rotate
+    (order 3, cval 0 in physical units), the velocity pair (channels 1, 2) rotated as a vector, re-normalised and
+    clipped to [0, 1] (``rescaled=False``: the physical field).  fp32 out (include/sr3d.h: sr3d_rotate_fields)."""
+    x = _rot_input(x, "rotate_fields: x")
+    m, s = _scales(means, scales)
+    workspace, wp, wn = _ws_ptr(workspace, x, coef_ready)
+    y = torch.empty_like(x)
+    flags = (L.ROTATE_COEF_READY if coef_ready else 0) | (0 if rescaled else L.ROTATE_PHYSICAL)
+    L.check(L.lib.sr3d_rotate_fields(L.dev_ptr(x, "rotate_fields: x"), L.dev_ptr(y), *[int(v) for v in x.shape], m, s,
+                                     float(angle), flags, wp, wn, L.stream_ptr()), "sr3d_rotate_fields")
+    return y
+
+
+def rotate_building(b: torch.Tensor, angle: float, th: float = 0.1, workspace: Optional[torch.Tensor] = None,
+                    coef_ready: bool = False) -> torch.Tensor:
+    """rotate_building_height of the reference (:49-60): cubic-spline rotation, rounded to fp32, then ``> th`` -> {0, 1}
+    (include/sr3d.h: sr3d_rotate_building)"""
+    b = _rot_input(b, "rotate_building: b")
+    workspace, wp, wn = _ws_ptr(workspace, b, coef_ready)
+    y = torch.empty_like(b)
+    L.check(L.lib.sr3d_rotate_building(L.dev_ptr(b, "rotate_building: b"), L.dev_ptr(y), *[int(v) for v in b.shape],
+                                       float(angle), float(th), L.ROTATE_COEF_READY if coef_ready else 0, wp, wn,
+                                       L.stream_ptr()), "sr3d_rotate_building")
+    return y
+
+
+def equivariance_errors(preds: torch.Tensor, preds_after_rot: torch.Tensor, means: Sequence[float],
+                        scales: Sequence[float], angle: float, sx: int, ex: int, sy: int, ey: int,
+                        workspace: Optional[torch.Tensor] = None, coef_ready: bool = False) -> torch.Tensor:
+    """the reference's errors (:63-158) after its two forwards, in one fused pass: ``preds`` rotated (clip included)
+    and compared with ``preds_after_rot`` over [..., sy:ey, sx:ex] without writing the rotated prediction.
+    Returns the fp64 means (tm, vr, vl_vp) on the device (include/sr3d.h: sr3d_equivariance_errors)."""
+    preds = _rot_input(preds, "equivariance_errors: preds")
+    par = _rot_input(preds_after_rot, "equivariance_errors: preds_after_rot")
+    B, c, Z, Y, X = preds.shape
+    if c != 4 or par.shape != preds.shape:
+        raise ValueError("equivariance_errors expects preds and preds_after_rot of one (B, 4, Z, Y, X) shape")
+    m, s = _scales(means, scales)
+    workspace, wp, wn = _ws_ptr(workspace, preds, coef_ready)
+    out = torch.empty(3, dtype=torch.float64, device=preds.device)
+    L.check(L.lib.sr3d_equivariance_errors(L.dev_ptr(preds, "equivariance_errors: preds"),
+                                           L.dev_ptr(par, "equivariance_errors: preds_after_rot"), B, Z, Y, X, m, s,
+                                           float(angle), int(sy), int(ey), int(sx), int(ex),
+                                           L.ROTATE_COEF_READY if coef_ready else 0, L.dev_ptr(out, dtype=torch.float64),
+                                           wp, wn, L.stream_ptr()), "sr3d_equivariance_errors")
+    return out
+
+
 def eval_shapes_ok(p: torch.Tensor, t: torch.Tensor, b: torch.Tensor) -> bool:
     """the fused evaluation pass takes (B,4,Z,Y,X) fields and a (B,1,Z,Y,X) mask"""
     return (p.dim() == 5 and p.shape[1] == 4 and t.shape == p.shape and b is not None and b.dim() == 5

@@ -259,6 +259,35 @@ size_t sr3d_eval_metrics_workspace_bytes(int B, int Z, int Y, int X);
 int sr3d_eval_metrics(const void* p, const void* t, const void* b, int B, int Z, int Y, int X, const float stds[4],
                       float delta_meter, int lev, void* out, void* workspace, void* stream);
 
+/* Rotation about the vertical axis (reference src/equivariance_error_calculator.py): every (y, x) plane of an NCDHW
+ * fp32 tensor rotated as scipy.ndimage.rotate(a, angle_deg, axes=(-2, -1), reshape=False) does it -- cubic B-spline
+ * (prefilter with the mirror boundary, fp64 coefficients), mode 'constant', cval = 0.  angle_deg is reduced modulo
+ * 360 on the host, with exact cos / sin at multiples of 90 degrees (scipy.special.cosdg / sindg).
+ * The workspace (sr3d_rotate_workspace_bytes of the rotated tensor's shape; C = 4 for sr3d_equivariance_errors)
+ * starts with the tensor's fp64 spline coefficients.  flags:
+ *   SR3D_ROTATE_COEF_READY  the workspace already holds the coefficients of THIS input (an earlier call on the same
+ *                           tensor and workspace, any angle): the prefilter is skipped -- an angle sweep pays it once;
+ *   SR3D_ROTATE_PHYSICAL    sr3d_rotate_fields only: return the physical field (rescaled = False), no clip. */
+enum { SR3D_ROTATE_COEF_READY = 1, SR3D_ROTATE_PHYSICAL = 2 };
+size_t sr3d_rotate_workspace_bytes(int B, int C, int Z, int Y, int X);
+/* rotate_temperature_velocity (equivariance_error_calculator.py:6-46): x (B, 4, Z, Y, X) normalised fields (T, u, v,
+ * w); HOST means[4], scales[4].  y = clip((Q @ rotate(x * scales + means) - means) / scales, 0, 1), Q mixing channels
+ * 1 and 2 by (cos, sin; -sin, cos) -- the velocity rotated as a vector.  C must be 4. */
+int sr3d_rotate_fields(const void* x, void* y, int B, int C, int Z, int Y, int X, const double means[4],
+                       const double scales[4], double angle_deg, int flags, void* workspace, size_t workspace_bytes,
+                       void* stream);
+/* rotate_building_height (:49-60): y = (float32(rotate(b)) > float32(th)) ? 1 : 0, any C */
+int sr3d_rotate_building(const void* b, void* y, int B, int C, int Z, int Y, int X, double angle_deg, double th,
+                         int flags, void* workspace, size_t workspace_bytes, void* stream);
+/* calc_preds_for_equivariance_errors + calc_equivariance_errors (:63-158) after the two forwards: preds and
+ * preds_after_rot (B, 4, Z, Y, X); R = scales * rotate_fields(preds) + means, A = scales * preds_after_rot + means;
+ * out (3 doubles, DEVICE) = means over [:, sy:ey, sx:ex] of |R_T - A_T|, |R_w - A_w| and ||(R_u, R_v) - (A_u, A_v)||
+ * (keys tm, vr, vl_vp), reduced deterministically in fp64.  The window bounds follow Python slices (negative = from
+ * the end); an empty window or one outside the plane is SR3D_E_ARG. */
+int sr3d_equivariance_errors(const void* preds, const void* preds_after_rot, int B, int Z, int Y, int X,
+                             const double means[4], const double scales[4], double angle_deg, int sy, int ey, int sx,
+                             int ex, int flags, void* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* SSIM3D (reference src/ssim.py:52-115: masked structural similarity with a w x w x w Gaussian or uniform window,
  * zero padding).  img1, img2: (B, C, Z, Y, X); mask: (B, Cm, Z, Y, X) with Cm = 1 or C; `window`: the n 1-D taps
  * (HOST array, n odd, <= 15) whose triple outer product is the reference's 3-D window; mean_out: 1 float (device) =
