@@ -36,6 +36,11 @@ class Slice(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("channels", C.c_int32)]
 
 
+class SurfaceSrc(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("C", C.c_int32), ("Zs", C.c_int32), ("channel", C.c_int32),
+                ("levels", C.c_int32), ("affine", C.c_int32), ("scale", C.c_float), ("mean", C.c_float)]
+
+
 class ConvDesc(C.Structure):
     _fields_ = [("B", C.c_int32), ("Cin", C.c_int32), ("Cout", C.c_int32), ("Z", C.c_int32), ("Y", C.c_int32),
                 ("X", C.c_int32), ("stride", C.c_int32), ("dtype", C.c_int32)]
@@ -83,6 +88,10 @@ SYMBOLS = {
     "sr3d_rotate_building": (_I, [_P, _P, _I, _I, _I, _I, _I, _D, _D, _I, _P, _SZ, _P]),
     "sr3d_equivariance_errors": (_I, [_P, _P, _I, _I, _I, _I, C.POINTER(_D), C.POINTER(_D), _D, _I, _I, _I, _I, _I, _P,
                                       _P, _SZ, _P]),
+    "sr3d_surface_temperature": (_I, [C.POINTER(SurfaceSrc), _I, _I, _I, _P, C.POINTER(_D), _I, _P, _P]),
+    "sr3d_surface_temperature_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "sr3d_surface_temperature_errors": (_I, [C.POINTER(SurfaceSrc), C.POINTER(SurfaceSrc), _I, _I, _I, _P,
+                                             C.POINTER(_D), _I, _P, _P, _P, _P, _SZ, _P]),
     "sr3d_ssim3d_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I]),
     "sr3d_ssim3d": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, C.POINTER(_F), _I, _F, _F, _P, _P, _P, _P]),
     "sr3d_adam_step": (_I, [_P, _P, _P, _P, _LL, _D, _D, _D, _D, _I, _D, _P]),

@@ -684,6 +684,103 @@ def equivariance_errors(preds: torch.Tensor, preds_after_rot: torch.Tensor, mean
     return out
 
 
+# ---------------------------------------------------------------- near-surface (2 m) temperature
+# zeroed workspaces of the fused 2 m call, per (device, stream): its ticket word starts at zero and every call leaves it
+# so (include/sr3d.h: sr3d_surface_temperature_workspace_bytes)
+_SURFACE_WS: dict = {}
+
+
+def surface_heights(levels: int, z0: float = 17.5, dz: float = 5.0):
+    """the level heights H_k = k * dz + z0 (fp64) as the HOST array the 2 m calls take (the notebook's HEIGHT_LEVELS:
+    np.arange(32) * 5 + 17.5)"""
+    if levels < 1:
+        raise ValueError(f"levels must be >= 1 (got {levels})")
+    return (C.c_double * levels)(*[float(k) * float(dz) + float(z0) for k in range(levels)])
+
+
+def _surface_src(t: torch.Tensor, channel: int, levels: int, scale, mean, what: str) -> L.SurfaceSrc:
+    if not t.is_cuda:
+        raise RuntimeError(f"{what} must live on the GPU: the sr3d engine has no CPU path")
+    if t.dim() != 5:
+        raise ValueError(f"{what} must be (B, C, Z, Y, X) (got {tuple(t.shape)})")
+    if (scale is None) != (mean is None):
+        raise ValueError(f"{what}: give both scale and mean, or neither")
+    _, c, zs, _, _ = t.shape
+    if not 0 <= channel < c:
+        raise ValueError(f"{what}: channel {channel} outside [0, {c})")
+    if not 1 <= levels <= zs:
+        raise ValueError(f"{what}: levels {levels} outside [1, {zs}]")
+    aff = scale is not None
+    return L.SurfaceSrc(L.dev_ptr(t, what).value, int(c), int(zs), int(channel), int(levels), int(aff),
+                        float(scale) if aff else 1.0, float(mean) if aff else 0.0)
+
+
+def _surface_tz(tz: torch.Tensor, shape, what: str) -> C.c_void_p:
+    if tuple(tz.shape) != tuple(shape):
+        raise ValueError(f"{what}: tz must be the (Y, X) = {tuple(shape)} building-top height map (got {tuple(tz.shape)})")
+    return L.dev_ptr(tz, f"{what}: tz", dtype=torch.float64)
+
+
+def surface_temperature(src: torch.Tensor, tz: torch.Tensor, *, channel: int = 0, levels: int = 32, z0: float = 17.5,
+                        dz: float = 5.0, scale: Optional[float] = None, mean: Optional[float] = None) -> torch.Tensor:
+    """infer_2m_height_temperature of the reference's make_2m_temperature notebook on the GPU: channel ``channel`` of
+    the (B, C, Zs, Y, X) fp32 ``src``, levels 0 .. levels-1 at heights k * dz + z0, extrapolated linearly in each (y, x)
+    column to the building / ground top ``tz`` ((Y, X) fp64, the transpose of read_building_height's array), read in
+    place.  ``scale``, ``mean``: dimensionalise first (``v * scale + mean`` in fp32, as torch does).  (B, Y, X) fp32,
+    NaN where the building tops the highest level (include/sr3d.h: sr3d_surface_temperature)."""
+    s = _surface_src(src, channel, levels, scale, mean, "surface_temperature: src")
+    B, _, _, Y, X = src.shape
+    tzp = _surface_tz(tz, (Y, X), "surface_temperature")
+    out = torch.empty(B, Y, X, dtype=torch.float32, device=src.device)
+    L.check(L.lib.sr3d_surface_temperature(C.byref(s), B, Y, X, tzp, surface_heights(levels, z0, dz), levels,
+                                           L.dev_ptr(out), L.stream_ptr()), "sr3d_surface_temperature")
+    return out
+
+
+def _surface_workspace(device: torch.device, nbytes: int) -> torch.Tensor:
+    key = (device.index, torch.cuda.current_stream(device).cuda_stream)
+    ws = _SURFACE_WS.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = _SURFACE_WS[key] = torch.zeros(nbytes, dtype=torch.uint8, device=device)
+    return ws
+
+
+def surface_temperature_errors(pred: torch.Tensor, truth: torch.Tensor, tz: torch.Tensor, *, pred_channel: int = 0,
+                               truth_channel: int = 0, levels: int = 32, truth_levels: Optional[int] = None,
+                               z0: float = 17.5, dz: float = 5.0, pred_scale: Optional[float] = None,
+                               pred_mean: Optional[float] = None, truth_scale: Optional[float] = None,
+                               truth_mean: Optional[float] = None, acc: Optional[torch.Tensor] = None,
+                               maps: bool = True):
+    """the 2 m maps of a prediction and of its truth and their error sums in ONE launch: ``pred`` (B, Cp, Zp, Y, X)
+    and ``truth`` (B, Ct, Zt, Y, X), each read in place with its own channel, level count (``truth_levels`` defaults to
+    ``levels``) and optional dimensionalisation.  ``acc`` (3 fp64 on the device; new and zeroed when None) +=
+    (sum (p - t)^2, sum |p - t|, count) over the columns where both maps are finite; it stays on the device, so a loop
+    over a test set makes no host round trip.  Returns (pred map, truth map, acc); ``maps=False`` writes no map and
+    returns None for both (include/sr3d.h: sr3d_surface_temperature_errors)."""
+    tl = levels if truth_levels is None else truth_levels
+    sp = _surface_src(pred, pred_channel, levels, pred_scale, pred_mean, "surface_temperature_errors: pred")
+    st = _surface_src(truth, truth_channel, tl, truth_scale, truth_mean, "surface_temperature_errors: truth")
+    B, _, _, Y, X = pred.shape
+    if truth.shape[0] != B or tuple(truth.shape[3:]) != (Y, X) or truth.device != pred.device:
+        raise ValueError(f"surface_temperature_errors: pred {tuple(pred.shape)} and truth {tuple(truth.shape)} differ in "
+                         "B, Y, X or device")
+    tzp = _surface_tz(tz, (Y, X), "surface_temperature_errors")
+    if acc is None:
+        acc = torch.zeros(3, dtype=torch.float64, device=pred.device)
+    if acc.numel() != 3:
+        raise ValueError("surface_temperature_errors: acc holds 3 doubles (sum sq, sum abs, count)")
+    accp = L.dev_ptr(acc, "surface_temperature_errors: acc", dtype=torch.float64)
+    pm = torch.empty(B, Y, X, dtype=torch.float32, device=pred.device) if maps else None
+    tm = torch.empty(B, Y, X, dtype=torch.float32, device=pred.device) if maps else None
+    nbytes = L.lib.sr3d_surface_temperature_workspace_bytes(B, Y, X)
+    ws = _surface_workspace(pred.device, nbytes)
+    nh = max(levels, tl)
+    L.check(L.lib.sr3d_surface_temperature_errors(C.byref(sp), C.byref(st), B, Y, X, tzp, surface_heights(nh, z0, dz),
+                                                  nh, L.dev_ptr(pm), L.dev_ptr(tm), accp, C.c_void_p(ws.data_ptr()),
+                                                  ws.numel(), L.stream_ptr()), "sr3d_surface_temperature_errors")
+    return pm, tm, acc
+
+
 def eval_shapes_ok(p: torch.Tensor, t: torch.Tensor, b: torch.Tensor) -> bool:
     """the fused evaluation pass takes (B,4,Z,Y,X) fields and a (B,1,Z,Y,X) mask"""
     return (p.dim() == 5 and p.shape[1] == 4 and t.shape == p.shape and b is not None and b.dim() == 5

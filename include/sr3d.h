@@ -288,6 +288,38 @@ int sr3d_equivariance_errors(const void* preds, const void* preds_after_rot, int
                              const double means[4], const double scales[4], double angle_deg, int sy, int ey, int sx,
                              int ex, int flags, void* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Near-surface (2 m) temperature (reference notebook make_2m_temperature: infer_2m_height_temperature, with the
+ * prediction dimensionalised as make_inference does).  A source is one channel of an NCDHW fp32 tensor, read in
+ * place: src[b, channel, k, y, x] for k < levels.  tz: (Y, X) fp64 building / ground top heights (DEVICE; the
+ * transpose of read_building_height's (i = x, j = y) array); heights: HOST, nheights (<= 128) strictly increasing
+ * fp64 level heights H[k] (reference: k * 5 + 17.5).  Per column, Z = levels: NaN if tz > H[Z-1]; first = 0 if
+ * !(tz > H[0]), else the first k with H[k] >= tz; t1 if first == Z-1; else, with t1, t2 the levels first, first + 1,
+ * float(double(t1) + ((tz - H[first]) * double(t2 - t1)) / (H[first+1] - H[first])) -- numpy >= 2's rounding of
+ * the notebook's expression (t2 - t1 in fp32, the rest in fp64).  affine != 0: every value read is first mapped to
+ * (v * scale) + mean, each step rounded to fp32 (torch's `data * scales + means`).  No alignment requirement. */
+typedef struct {
+  const void* data;     /* (B, C, Zs, Y, X) fp32, dense */
+  int32_t C, Zs;
+  int32_t channel;      /* 0 <= channel < C */
+  int32_t levels;       /* 1 <= levels <= Zs, and <= nheights */
+  int32_t affine;
+  float scale, mean;
+} sr3d_surface_src_t;
+/* the map alone: out (B, Y, X) fp32 */
+int sr3d_surface_temperature(const sr3d_surface_src_t* src, int B, int Y, int X, const void* tz,
+                             const double* heights, int nheights, void* out, void* stream);
+/* workspace of sr3d_surface_temperature_errors: a ticket word, then one fp64 partial triple per workgroup.  The
+ * ticket must be ZERO before the first call (allocate the workspace zeroed); every call leaves it zero. */
+size_t sr3d_surface_temperature_workspace_bytes(int B, int Y, int X);
+/* prediction and truth in ONE launch (each with its own C, Zs, channel, levels, affine; one B, Y, X, tz, heights):
+ * both maps (pred_out, truth_out: (B, Y, X) fp32, each may be NULL), and acc (3 doubles, DEVICE) += (sum (p - t)^2,
+ * sum |p - t|, count) over the columns where both maps are finite, differences in fp64.  Deterministic: per sample a
+ * fixed-order sum, the samples added to acc in order -- two calls on two batches equal one call on both. */
+int sr3d_surface_temperature_errors(const sr3d_surface_src_t* pred, const sr3d_surface_src_t* truth, int B, int Y,
+                                    int X, const void* tz, const double* heights, int nheights, void* pred_out,
+                                    void* truth_out, void* acc, void* workspace, size_t workspace_bytes,
+                                    void* stream);
+
 /* SSIM3D (reference src/ssim.py:52-115: masked structural similarity with a w x w x w Gaussian or uniform window,
  * zero padding).  img1, img2: (B, C, Z, Y, X); mask: (B, Cm, Z, Y, X) with Cm = 1 or C; `window`: the n 1-D taps
  * (HOST array, n odd, <= 15) whose triple outer product is the reference's 3-D window; mean_out: 1 float (device) =
