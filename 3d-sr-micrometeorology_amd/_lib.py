@@ -41,6 +41,13 @@ class SurfaceSrc(C.Structure):
                 ("levels", C.c_int32), ("affine", C.c_int32), ("scale", C.c_float), ("mean", C.c_float)]
 
 
+class LrDataParams(C.Structure):
+    _fields_ = [("raw", C.c_void_p), ("channel_stride", C.c_longlong), ("C", C.c_int32), ("Z", C.c_int32),
+                ("Y", C.c_int32), ("X", C.c_int32), ("scale", C.c_int32), ("hr_margin", C.c_int32),
+                ("align_nan", C.c_int32), ("hr_mask", C.c_void_p), ("lr_tops", C.c_void_p), ("lat", C.c_void_p),
+                ("lon", C.c_void_p), ("lev", C.c_void_p), ("hr_out", C.c_void_p), ("lr_out", C.c_void_p)]
+
+
 class ConvDesc(C.Structure):
     _fields_ = [("B", C.c_int32), ("Cin", C.c_int32), ("Cout", C.c_int32), ("Z", C.c_int32), ("Y", C.c_int32),
                 ("X", C.c_int32), ("stride", C.c_int32), ("dtype", C.c_int32)]
@@ -92,6 +99,8 @@ SYMBOLS = {
     "sr3d_surface_temperature_workspace_bytes": (_SZ, [_I, _I, _I]),
     "sr3d_surface_temperature_errors": (_I, [C.POINTER(SurfaceSrc), C.POINTER(SurfaceSrc), _I, _I, _I, _P,
                                              C.POINTER(_D), _I, _P, _P, _P, _P, _SZ, _P]),
+    "sr3d_lrdata_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "sr3d_lrdata": (_I, [C.POINTER(LrDataParams), _P, _SZ, _P]),
     "sr3d_ssim3d_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I]),
     "sr3d_ssim3d": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, C.POINTER(_F), _I, _F, _F, _P, _P, _P, _P]),
     "sr3d_adam_step": (_I, [_P, _P, _P, _P, _LL, _D, _D, _D, _D, _I, _D, _P]),

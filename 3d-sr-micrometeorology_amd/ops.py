@@ -781,6 +781,79 @@ def surface_temperature_errors(pred: torch.Tensor, truth: torch.Tensor, tz: torc
     return pm, tm, acc
 
 
+# ---------------------------------------------------------------- LR training data from HR fields
+LRDATA_SCALE = 4   # the reference's script asserts SR_SCALE == 4; the kernel implements only it
+
+
+def _lrdata_coord(v, n: int, what: str, device) -> Optional[torch.Tensor]:
+    if v is None:
+        return None
+    t = torch.as_tensor(v, dtype=torch.float64).reshape(-1)
+    if t.numel() != n:
+        raise ValueError(f"coarse_grain_outside_buildings: {what} holds {t.numel()} values, {n} needed")
+    c = t.cpu()
+    if not bool(torch.isfinite(c).all()) or (n > 1 and not bool((c[1:] > c[:-1]).all())):
+        raise ValueError(f"coarse_grain_outside_buildings: {what} must be finite and strictly increasing "
+                         "(xarray's interpolate_na requires a monotonic coordinate)")
+    return t.to(device).contiguous()
+
+
+def coarse_grain_outside_buildings(raw: torch.Tensor, hr_mask: torch.Tensor, lr_tops: torch.Tensor, *,
+                                   scale: int = LRDATA_SCALE, hr_margin: int = 40, lat=None, lon=None, lev=None,
+                                   align_nan: bool = True):
+    """one time step of the reference's make_dl_data_using_outside_lr_builds on the GPU: ``raw`` (C, Z, Y, X) fp32,
+    read in place (each channel dense; any channel stride), ``hr_mask`` (Z, Y, X) bool / uint8 (1 = in a building or
+    NaN in tm), ``lr_tops`` (2, Y/4, X/4) int32: per LR column the number of masked HR levels (the resized LR buildings)
+    and of masked LR levels (training_data_maker.lr_building_tops).  ``lat`` (Y), ``lon`` (X), ``lev`` (Z): fp64
+    coordinates of the nearest fill, strictly increasing; None gives index coordinates.  ``align_nan``: channels > 0
+    are NaN where channel 0 is (the reference's align_nan_grids).  Returns (hr_out (C, Z, Y-2m, X-2m), lr_out
+    (C, Z/4, (Y-2m)/4, (X-2m)/4)), fp32 on the device, m = hr_margin (include/sr3d.h: sr3d_lrdata)."""
+    what = "coarse_grain_outside_buildings"
+    if not raw.is_cuda:
+        raise RuntimeError(f"{what}: raw must live on the GPU: the sr3d engine has no CPU path")
+    if raw.dim() != 4 or raw.dtype != torch.float32:
+        raise ValueError(f"{what}: raw must be (C, Z, Y, X) float32 (got {tuple(raw.shape)} {raw.dtype})")
+    Cn, Z, Y, X = raw.shape
+    if scale != LRDATA_SCALE:
+        raise ValueError(f"{what}: scale {scale}: only {LRDATA_SCALE} is implemented (the reference asserts it)")
+    if Z % scale or Y % scale or X % scale:
+        raise ValueError(f"{what}: (Z, Y, X) = {(Z, Y, X)} must be multiples of {scale}")
+    if hr_margin < 0 or hr_margin % scale or 2 * hr_margin >= min(Y, X):
+        raise ValueError(f"{what}: hr_margin {hr_margin} must be a multiple of {scale} that leaves a window of "
+                         f"{(Y, X)}")
+    if tuple(raw.stride()[1:]) != (Y * X, X, 1) or (Cn > 1 and raw.stride(0) < Z * Y * X):
+        raise ValueError(f"{what}: every channel of raw must be a dense (Z, Y, X) volume (strides {raw.stride()})")
+    if tuple(hr_mask.shape) != (Z, Y, X):
+        raise ValueError(f"{what}: hr_mask must be (Z, Y, X) = {(Z, Y, X)} (got {tuple(hr_mask.shape)})")
+    if hr_mask.dtype == torch.bool:
+        hr_mask = hr_mask.view(torch.uint8)
+    if tuple(lr_tops.shape) != (2, Y // scale, X // scale):
+        raise ValueError(f"{what}: lr_tops must be (2, Y/{scale}, X/{scale}) = {(2, Y // scale, X // scale)} "
+                         f"(got {tuple(lr_tops.shape)})")
+    if hr_mask.device != raw.device or lr_tops.device != raw.device:
+        raise ValueError(f"{what}: raw, hr_mask and lr_tops must be on one device")
+    latd = _lrdata_coord(lat, Y, "lat", raw.device)
+    lond = _lrdata_coord(lon, X, "lon", raw.device)
+    levh = None
+    if lev is not None:
+        lv = _lrdata_coord(lev, Z, "lev", "cpu")
+        levh = (C.c_double * Z)(*lv.tolist())
+    m = hr_margin
+    hr = torch.empty(Cn, Z, Y - 2 * m, X - 2 * m, dtype=torch.float32, device=raw.device)
+    lr = torch.empty(Cn, Z // scale, (Y - 2 * m) // scale, (X - 2 * m) // scale, dtype=torch.float32,
+                     device=raw.device)
+    ws = torch.empty(L.lib.sr3d_lrdata_workspace_bytes(Cn, Y, X), dtype=torch.uint8, device=raw.device)
+    prm = L.LrDataParams(raw.data_ptr(), raw.stride(0), Cn, Z, Y, X, scale, m, int(bool(align_nan)),
+                         L.dev_ptr(hr_mask, f"{what}: hr_mask", dtype=torch.uint8).value,
+                         L.dev_ptr(lr_tops, f"{what}: lr_tops", dtype=torch.int32).value,
+                         L.dev_ptr(latd, f"{what}: lat", dtype=torch.float64).value,
+                         L.dev_ptr(lond, f"{what}: lon", dtype=torch.float64).value,
+                         C.cast(levh, C.c_void_p).value if levh is not None else None,
+                         L.dev_ptr(hr).value, L.dev_ptr(lr).value)
+    L.check(L.lib.sr3d_lrdata(C.byref(prm), C.c_void_p(ws.data_ptr()), ws.numel(), L.stream_ptr()), "sr3d_lrdata")
+    return hr, lr
+
+
 def eval_shapes_ok(p: torch.Tensor, t: torch.Tensor, b: torch.Tensor) -> bool:
     """the fused evaluation pass takes (B,4,Z,Y,X) fields and a (B,1,Z,Y,X) mask"""
     return (p.dim() == 5 and p.shape[1] == 4 and t.shape == p.shape and b is not None and b.dim() == 5

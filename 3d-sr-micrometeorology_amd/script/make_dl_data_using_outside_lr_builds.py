@@ -1,0 +1,199 @@
+#!/usr/bin/env python3
+"""Training data from LES output: the reference's datascience/script/make_dl_data_using_outside_lr_builds.py with
+the per-time-step work on the GPU (ops.coarse_grain_outside_buildings, one call per time step for all channels).
+
+It writes the reference's tree, skipping files that exist:
+    <out_dir>/<data_group>/<YYYYMMDD>/<YYYYmmddTHHMMSS>_HR.npy      (4, Z, Y-2m, X-2m) float32
+    <out_dir>/<data_group>/<YYYYMMDD>/<YYYYmmddTHHMMSS>_LR_x04.npy  (4, Z/4, (Y-2m)/4, (X-2m)/4) float32
+    <out_dir>/<data_group>/hr_is_in_build.npy, lr_is_in_build.npy   the masks, tiled over the 4 channels, float64
+with m = --hr_margin (40) and the LR margin m / 4.
+
+--raw_dir DIR   one full-domain ``<YYYYmmddTHHMMSS>.npy`` (4, Z, Y, X) per time step, channels tm, vl, vp, vr, the
+                GrADS undef already NaN (converting GrADS output to these files is the user's job).  Levels are
+                z0 + k dz (--z0 / --dz); the buildings come from --hr_building_path / --lr_building_path (EleTopoZ
+                files).  Every --time_sample_interval-th step is kept, counted from the last one, as the reference
+                does; the HR mask is the HR buildings OR NaN in tm at the first kept step.  Faithful to the
+                reference.
+--from_hr DIR   regenerate ``*_LR_x04.npy`` for an existing tree DIR/<data_group>/<date>/*_HR.npy (margins already
+                cut) into <out_dir> (default DIR), with the HR mask taken as isnan(tm) of each file and the LR
+                buildings of --lr_building_path cut by m / 4.  One difference from the reference: the fill sees only
+                the cut window, so a fully-NaN column whose nearest valid column lies in the cut margin takes a
+                different source column, and the LR blocks it falls in differ.
+
+    python 3d-sr-micrometeorology_amd/script/make_dl_data_using_outside_lr_builds.py --raw_dir raw/20150731 \\
+        --out_dir data/DL_data --hr_building_path EleTopoZ_HR.txt --lr_building_path EleTopoZ_LR.txt
+"""
+import argparse
+import datetime
+import glob
+import logging
+import os
+import pathlib
+import sys
+
+ROOT = str(pathlib.Path(__file__).resolve().parents[2])
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+
+logger = logging.getLogger()
+
+SR_SCALE = 4
+VAR_NAMES = ["tm", "vl", "vp", "vr"]
+STAMP = "%Y%m%dT%H%M%S"
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    src = p.add_mutually_exclusive_group(required=True)
+    src.add_argument("--raw_dir", type=str, help="full-domain <stamp>.npy files (4, Z, Y, X) per time step")
+    src.add_argument("--from_hr", type=str, help="an existing tree whose *_HR.npy files give the LR files")
+    p.add_argument("--out_dir", type=str, default=None, help="root of the tree to write (default: --from_hr)")
+    p.add_argument("--data_group", type=str, default="10")
+    p.add_argument("--hr_building_path", type=str, default=None)
+    p.add_argument("--lr_building_path", type=str, required=True)
+    p.add_argument("--z0", type=float, default=17.5, help="height of level 0 (m)")
+    p.add_argument("--dz", type=float, default=5.0, help="level spacing (m)")
+    p.add_argument("--hr_margin", type=int, default=40)
+    p.add_argument("--time_sample_interval", type=int, default=2)
+    p.add_argument("--device", type=str, default="cuda")
+    a = p.parse_args(argv)
+    if a.out_dir is None:
+        if a.from_hr is None:
+            p.error("--out_dir is required with --raw_dir")
+        a.out_dir = a.from_hr
+    if a.raw_dir is not None and a.hr_building_path is None:
+        p.error("--hr_building_path is required with --raw_dir")
+    if a.hr_margin <= 0 or a.hr_margin % SR_SCALE:
+        p.error(f"--hr_margin must be a positive multiple of {SR_SCALE}")
+    if a.time_sample_interval < 1:
+        p.error("--time_sample_interval must be >= 1")
+    return a
+
+
+def stamp_of(path: str) -> datetime.datetime:
+    return datetime.datetime.strptime(os.path.basename(path).split(".")[0].split("_")[0], STAMP)
+
+
+def sample_times(paths, interval: int):
+    """every interval-th entry, counted from the last one (reference: times[::-1][::interval][::-1])"""
+    return list(paths)[::-1][::interval][::-1]
+
+
+def raw_files(raw_dir: str):
+    """the <stamp>.npy files of raw_dir in time order (other names are ignored)"""
+    files = []
+    for f in glob.glob(os.path.join(raw_dir, "*.npy")):
+        try:
+            stamp_of(f)
+        except ValueError:
+            continue
+        files.append(f)
+    return sorted(files, key=stamp_of)
+
+
+def out_paths(out_dir: str, group: str, stamp: datetime.datetime):
+    d = pathlib.Path(out_dir) / group / f"{stamp:%Y%m%d}"
+    return d / f"{stamp:{STAMP}}_HR.npy", d / f"{stamp:{STAMP}}_LR_x{SR_SCALE:02}.npy"
+
+
+def save(path, data: np.ndarray) -> bool:
+    path = pathlib.Path(path)
+    if path.exists():
+        return False
+    path.parent.mkdir(parents=True, exist_ok=True)
+    np.save(str(path), np.ascontiguousarray(data))
+    logger.info(f"{path} has been made")
+    return True
+
+
+def building_yx(path: str, col: str) -> np.ndarray:
+    from sr3d_amd.src.building_height_helper import read_building_height
+    return read_building_height(path, col, margin=0).transpose()
+
+
+def _tile(mask: np.ndarray) -> np.ndarray:
+    return np.tile(mask[None].astype(np.float64), (len(VAR_NAMES), 1, 1, 1))
+
+
+def run_raw(a):
+    import torch
+    from sr3d_amd import ops
+    from sr3d_amd.src.building_height_helper import calc_is_in_building
+    from sr3d_amd.src.training_data_maker import lr_building_tops
+
+    files = sample_times(raw_files(a.raw_dir), a.time_sample_interval)
+    if not files:
+        raise FileNotFoundError(f"no <{STAMP}>.npy files in {a.raw_dir}")
+    dev = torch.device(a.device)
+    hr_tz, hr_ez = building_yx(a.hr_building_path, "Tz"), building_yx(a.hr_building_path, "Ez")
+    lr_tz, lr_ez = building_yx(a.lr_building_path, "Tz"), building_yx(a.lr_building_path, "Ez")
+    m, ml = a.hr_margin, a.hr_margin // SR_SCALE
+    group = pathlib.Path(a.out_dir) / a.data_group
+    hr_mask = tops = levs = None
+    for f in files:
+        hr_file, lr_file = out_paths(a.out_dir, a.data_group, stamp_of(f))
+        if hr_mask is None:                              # the first kept time step fixes the HR mask
+            raw0 = np.load(f, mmap_mode="r")
+            _, Z, Y, X = raw0.shape
+            assert (Y, X) == hr_tz.shape and (Y // SR_SCALE, X // SR_SCALE) == lr_tz.shape
+            levs = np.arange(Z, dtype=np.float64) * a.dz + a.z0
+            hm = (calc_is_in_building(hr_tz, hr_ez, levs) + np.isnan(raw0[0]).astype(float)) > 0
+            save(group / "hr_is_in_build.npy", _tile(hm)[..., m:-m, m:-m])
+            lz = calc_is_in_building(lr_tz, lr_ez, levs[::SR_SCALE])
+            save(group / "lr_is_in_build.npy", _tile(lz)[..., ml:-ml, ml:-ml])
+            hr_mask = torch.from_numpy(hm).to(dev)
+            tops = torch.from_numpy(lr_building_tops(lr_tz, lr_ez, levs, SR_SCALE)).to(dev)
+        if hr_file.exists() and lr_file.exists():
+            continue
+        raw = torch.from_numpy(np.ascontiguousarray(np.load(f), dtype=np.float32)).to(dev)
+        hr, lr = ops.coarse_grain_outside_buildings(raw, hr_mask, tops, scale=SR_SCALE, hr_margin=m, lev=levs,
+                                                    align_nan=True)
+        save(hr_file, hr.cpu().numpy())
+        save(lr_file, lr.cpu().numpy())
+
+
+def run_from_hr(a):
+    import torch
+    from sr3d_amd import ops
+    from sr3d_amd.src.building_height_helper import calc_is_in_building
+    from sr3d_amd.src.training_data_maker import lr_building_tops
+
+    hr_files = sorted(glob.glob(os.path.join(a.from_hr, a.data_group, "*", "*_HR.npy")))
+    if not hr_files:
+        raise FileNotFoundError(f"no */*_HR.npy files in {os.path.join(a.from_hr, a.data_group)}")
+    dev = torch.device(a.device)
+    ml = a.hr_margin // SR_SCALE
+    lr_tz = building_yx(a.lr_building_path, "Tz")[ml:-ml, ml:-ml]
+    lr_ez = building_yx(a.lr_building_path, "Ez")[ml:-ml, ml:-ml]
+    tops = levs = None
+    for f in hr_files:
+        _, lr_file = out_paths(a.out_dir, a.data_group, stamp_of(f))
+        if lr_file.exists():
+            continue
+        hr = torch.from_numpy(np.ascontiguousarray(np.load(f), dtype=np.float32)).to(dev)
+        _, Z, Y, X = hr.shape
+        if tops is None:
+            assert (Y // SR_SCALE, X // SR_SCALE) == lr_tz.shape, "the HR files and the cut LR buildings differ"
+            levs = np.arange(Z, dtype=np.float64) * a.dz + a.z0
+            tops = torch.from_numpy(lr_building_tops(lr_tz, lr_ez, levs, SR_SCALE)).to(dev)
+            save(pathlib.Path(a.out_dir) / a.data_group / "lr_is_in_build.npy",
+                 _tile(calc_is_in_building(lr_tz, lr_ez, levs[::SR_SCALE])))
+        _, lr = ops.coarse_grain_outside_buildings(hr, torch.isnan(hr[0]), tops, scale=SR_SCALE, hr_margin=0,
+                                                   lev=levs, align_nan=True)
+        save(lr_file, lr.cpu().numpy())
+
+
+def main(argv=None):
+    logging.basicConfig(level=logging.INFO, format="%(message)s", stream=sys.stdout)
+    a = parse_args(argv)
+    import sr3d_amd  # noqa: F401  (loads the engine before any work)
+    if a.raw_dir is not None:
+        run_raw(a)
+    else:
+        run_from_hr(a)
+
+
+if __name__ == "__main__":
+    main()

@@ -320,6 +320,35 @@ int sr3d_surface_temperature_errors(const sr3d_surface_src_t* pred, const sr3d_s
                                     void* truth_out, void* acc, void* workspace, size_t workspace_bytes,
                                     void* stream);
 
+/* LR training data from one HR time step, building-aware (reference datascience/: training_data_maker.make_coarse_
+ * grained_dataarray_with_outside_lr_buildings and the script make_dl_data_using_outside_lr_builds, SR_SCALE 4).
+ * Per channel, a cell is valid when hr_mask is 0 there, the value is not NaN and (align_nan, channel > 0) channel 0
+ * is not NaN there.  Invalid cells are filled as xarray's interpolate_na(method="nearest", fill_value="extrapolate")
+ * along lev, then lat, then lon does (scipy interp1d: ties to the lower coordinate, edge values past the ends); cells
+ * z < lr_tops[0][y/4][x/4] then become NaN; each 4x4x4 block is the fp64 mean of its 64 cells, summed in numpy's
+ * pairwise order, rounded once to fp32, NaN if any cell is NaN; LR levels kz < lr_tops[1][Y/4][X/4] are NaN.
+ *   hr_out = raw with invalid cells NaN, the window [m, Y-m) x [m, X-m):     (C, Z, Y-2m, X-2m) fp32, dense
+ *   lr_out = the blocks of that window:                                      (C, Z/4, (Y-2m)/4, (X-2m)/4) fp32, dense
+ * Coordinates must increase strictly; NULL gives index coordinates.  Z <= 128; Z, Y, X, hr_margin multiples of 4.
+ * Three launches on `stream` (workspace init, column map, main pass), no host synchronisation. */
+typedef struct {
+  const void* raw;            /* (C, Z, Y, X) fp32: channel c at raw + c * channel_stride floats, each (Z, Y, X) dense */
+  long long channel_stride;   /* >= Z * Y * X */
+  int32_t C, Z, Y, X;
+  int32_t scale;              /* must be 4 */
+  int32_t hr_margin;          /* m: lateral cells cut from each edge of both outputs */
+  int32_t align_nan;          /* channels > 0 are invalid where channel 0 is NaN (reference align_nan_grids) */
+  const void* hr_mask;        /* (Z, Y, X) uint8, non-zero = masked */
+  const void* lr_tops;        /* (2, Y/4, X/4) int32: masked HR levels, masked LR levels per LR column */
+  const double* lat;          /* DEVICE (Y) fp64 or NULL */
+  const double* lon;          /* DEVICE (X) fp64 or NULL */
+  const double* lev;          /* HOST (Z) fp64 or NULL */
+  void* hr_out;
+  void* lr_out;
+} sr3d_lrdata_params_t;
+size_t sr3d_lrdata_workspace_bytes(int C, int Y, int X);
+int sr3d_lrdata(const sr3d_lrdata_params_t* params, void* workspace, size_t workspace_bytes, void* stream);
+
 /* SSIM3D (reference src/ssim.py:52-115: masked structural similarity with a w x w x w Gaussian or uniform window,
  * zero padding).  img1, img2: (B, C, Z, Y, X); mask: (B, Cm, Z, Y, X) with Cm = 1 or C; `window`: the n 1-D taps
  * (HOST array, n odd, <= 15) whose triple outer product is the reference's 3-D window; mean_out: 1 float (device) =
