@@ -48,6 +48,13 @@ class LrDataParams(C.Structure):
                 ("lon", C.c_void_p), ("lev", C.c_void_p), ("hr_out", C.c_void_p), ("lr_out", C.c_void_p)]
 
 
+class GradsParams(C.Structure):
+    _fields_ = [("X", C.c_int32), ("Y", C.c_int32), ("Z", C.c_int32), ("byteswap", C.c_int32), ("yrev", C.c_int32),
+                ("zrev", C.c_int32), ("align_nan", C.c_int32), ("level_offset", C.c_longlong * 4),
+                ("level_pitch", C.c_longlong * 4), ("src_bytes", C.c_longlong * 4), ("undef", C.c_double * 4),
+                ("out", C.c_void_p), ("tm_is_nan", C.c_void_p)]
+
+
 class ConvDesc(C.Structure):
     _fields_ = [("B", C.c_int32), ("Cin", C.c_int32), ("Cout", C.c_int32), ("Z", C.c_int32), ("Y", C.c_int32),
                 ("X", C.c_int32), ("stride", C.c_int32), ("dtype", C.c_int32)]
@@ -101,6 +108,7 @@ SYMBOLS = {
                                              C.POINTER(_D), _I, _P, _P, _P, _P, _SZ, _P]),
     "sr3d_lrdata_workspace_bytes": (_SZ, [_I, _I, _I]),
     "sr3d_lrdata": (_I, [C.POINTER(LrDataParams), _P, _SZ, _P]),
+    "sr3d_grads_decode": (_I, [C.POINTER(C.c_void_p), C.POINTER(GradsParams), _P]),
     "sr3d_ssim3d_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I]),
     "sr3d_ssim3d": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, C.POINTER(_F), _I, _F, _F, _P, _P, _P, _P]),
     "sr3d_adam_step": (_I, [_P, _P, _P, _P, _LL, _D, _D, _D, _D, _I, _D, _P]),

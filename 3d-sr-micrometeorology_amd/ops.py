@@ -854,6 +854,60 @@ def coarse_grain_outside_buildings(raw: torch.Tensor, hr_mask: torch.Tensor, lr_
     return hr, lr
 
 
+# ---------------------------------------------------------------- GrADS decode (the LES's raw output -> fields)
+def _four(v, cast, what: str):
+    vals = [cast(x) for x in v] if isinstance(v, (list, tuple)) else [cast(v)] * 4
+    if len(vals) != 4:
+        raise ValueError(f"grads_decode: {what} must be one value or one per variable (4), got {len(vals)}")
+    return vals
+
+
+def grads_decode(buffers, *, shape, level_offset, level_pitch, undef, byteswap: bool, yrev: bool = False,
+                 zrev: bool = False, align_nan: bool = True, want_tm_mask: bool = False):
+    """one time step of the LES's GrADS output on the GPU (include/sr3d.h: sr3d_grads_decode).  ``buffers``: four
+    uint8 device tensors (tm, vl, vp, vr), each the raw bytes of the step's level window as they lie in the data file;
+    ``shape`` = (Z, Y, X); ``level_offset`` / ``level_pitch``: bytes to the first value of file level 0 and between
+    level slabs (one value, or one per variable; `options sequential` files have offset 4 and pitch Y*X*4 + 8);
+    ``undef``: the descriptor's value(s), compared as fp32; ``byteswap``: the file is big endian; ``yrev`` / ``zrev``:
+    the file's rows / levels run downwards; ``align_nan``: vl, vp, vr are NaN where tm is (the reference's
+    align_nan_grids).  Returns the (4, Z, Y, X) fp32 tensor, with ``want_tm_mask`` also isnan(tm) as (Z, Y, X) uint8."""
+    what = "grads_decode"
+    if len(buffers) != 4:
+        raise ValueError(f"{what}: four buffers (tm, vl, vp, vr) needed, got {len(buffers)}")
+    Z, Y, X = (int(s) for s in shape)
+    if min(Z, Y, X) <= 0:
+        raise ValueError(f"{what}: shape (Z, Y, X) = {(Z, Y, X)} must be positive")
+    offs, pitches = _four(level_offset, int, "level_offset"), _four(level_pitch, int, "level_pitch")
+    undefs = _four(undef, float, "undef")
+    dev = buffers[0].device
+    for v, b in enumerate(buffers):
+        if not b.is_cuda:
+            raise RuntimeError(f"{what}: buffers[{v}] must live on the GPU: the sr3d engine has no CPU path")
+        if b.dtype != torch.uint8 or b.dim() != 1 or not b.is_contiguous():
+            raise ValueError(f"{what}: buffers[{v}] must be a contiguous 1-D uint8 tensor (got {tuple(b.shape)} "
+                             f"{b.dtype})")
+        if b.device != dev:
+            raise ValueError(f"{what}: the buffers must be on one device")
+        if offs[v] < 0 or offs[v] % 4 or pitches[v] % 4 or b.data_ptr() % 4:
+            raise ValueError(f"{what}: buffers[{v}]: address, level_offset {offs[v]} and level_pitch {pitches[v]} "
+                             "must be multiples of 4")
+        if pitches[v] < Y * X * 4:
+            raise ValueError(f"{what}: buffers[{v}]: level_pitch {pitches[v]} < one slab of {Y * X * 4} bytes")
+        need = offs[v] + (Z - 1) * pitches[v] + Y * X * 4
+        if b.numel() < need:
+            raise ValueError(f"{what}: buffers[{v}] holds {b.numel()} bytes, {need} needed")
+    out = torch.empty(4, Z, Y, X, dtype=torch.float32, device=dev)
+    mask = torch.empty(Z, Y, X, dtype=torch.uint8, device=dev) if want_tm_mask else None
+    i4, q4, d4 = C.c_longlong * 4, C.c_void_p * 4, C.c_double * 4
+    prm = L.GradsParams(X, Y, Z, int(bool(byteswap)), int(bool(yrev)), int(bool(zrev)), int(bool(align_nan)),
+                        i4(*offs), i4(*pitches), i4(*(b.numel() for b in buffers)), d4(*undefs), out.data_ptr(),
+                        mask.data_ptr() if mask is not None else None)
+    with torch.cuda.device(dev):
+        L.check(L.lib.sr3d_grads_decode(q4(*(b.data_ptr() for b in buffers)), C.byref(prm), L.stream_ptr()),
+                "sr3d_grads_decode")
+    return (out, mask) if want_tm_mask else out
+
+
 def eval_shapes_ok(p: torch.Tensor, t: torch.Tensor, b: torch.Tensor) -> bool:
     """the fused evaluation pass takes (B,4,Z,Y,X) fields and a (B,1,Z,Y,X) mask"""
     return (p.dim() == 5 and p.shape[1] == 4 and t.shape == p.shape and b is not None and b.dim() == 5

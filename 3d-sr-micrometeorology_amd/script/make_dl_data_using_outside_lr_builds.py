@@ -8,12 +8,24 @@ It writes the reference's tree, skipping files that exist:
     <out_dir>/<data_group>/hr_is_in_build.npy, lr_is_in_build.npy   the masks, tiled over the 4 channels, float64
 with m = --hr_margin (40) and the LR margin m / 4.
 
+Three input modes, one of them per run:
+
+--grads_dir DIR the LES's own GrADS output, read directly: DIR/atmos_<nest_level>_{tm,vl,vp,vr}.ctl and their data
+                files (src/io_grads.py; no xgrads, xarray or dask, no intermediate files).  --root_result_dir ROOT
+                with --target_datetime 2015-07-31T05:00:00 names DIR as the reference does
+                (ROOT/<datetime>/micro-meteorology/out/grads).  The first --discarded_initial_period (10) time steps
+                are dropped and the levels [--min_index_height (4), + --num_levels (40)) kept; the level heights
+                come from the descriptor's zdef and the time stamps from its tdef (--z0 / --dz are not used).  Per
+                kept step the four level-window byte ranges are copied from the memory-mapped files into a pinned
+                buffer, sent to the device and decoded there (ops.grads_decode: byte order, undef -> NaN, vl / vp /
+                vr NaN where tm is) on a side stream, one step ahead of the step being coarse-grained
+                (training_data_maker.AtmosData.steps: two staging sets, reused in event order).  What it
+                writes is what --raw_dir writes from the same fields.
 --raw_dir DIR   one full-domain ``<YYYYmmddTHHMMSS>.npy`` (4, Z, Y, X) per time step, channels tm, vl, vp, vr, the
-                GrADS undef already NaN (converting GrADS output to these files is the user's job).  Levels are
-                z0 + k dz (--z0 / --dz); the buildings come from --hr_building_path / --lr_building_path (EleTopoZ
-                files).  Every --time_sample_interval-th step is kept, counted from the last one, as the reference
+                GrADS undef already NaN.  Levels are z0 + k dz (--z0 / --dz); the buildings come from
+                --hr_building_path / --lr_building_path (EleTopoZ files).  Every --time_sample_interval-th step is kept, counted from the last one, as the reference
                 does; the HR mask is the HR buildings OR NaN in tm at the first kept step.  Faithful to the
-                reference.
+                reference.  (--grads_dir samples the time steps and builds the masks in the same way.)
 --from_hr DIR   regenerate ``*_LR_x04.npy`` for an existing tree DIR/<data_group>/<date>/*_HR.npy (margins already
                 cut) into <out_dir> (default DIR), with the HR mask taken as isnan(tm) of each file and the LR
                 buildings of --lr_building_path cut by m / 4.  One difference from the reference: the fill sees only
@@ -21,6 +33,9 @@ with m = --hr_margin (40) and the LR margin m / 4.
                 different source column, and the LR blocks it falls in differ.
 
     python 3d-sr-micrometeorology_amd/script/make_dl_data_using_outside_lr_builds.py --raw_dir raw/20150731 \\
+        --out_dir data/DL_data --hr_building_path EleTopoZ_HR.txt --lr_building_path EleTopoZ_LR.txt
+    python 3d-sr-micrometeorology_amd/script/make_dl_data_using_outside_lr_builds.py \\
+        --root_result_dir /data/mssg-results/tokyo_05m --target_datetime 2015-07-31T05:00:00 \\
         --out_dir data/DL_data --hr_building_path EleTopoZ_HR.txt --lr_building_path EleTopoZ_LR.txt
 """
 import argparse
@@ -47,6 +62,8 @@ STAMP = "%Y%m%dT%H%M%S"
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     src = p.add_mutually_exclusive_group(required=True)
+    src.add_argument("--grads_dir", type=str, help="the LES's GrADS output: atmos_<nest>_{tm,vl,vp,vr}.ctl + data")
+    src.add_argument("--root_result_dir", type=str, help="with --target_datetime: the reference's result tree")
     src.add_argument("--raw_dir", type=str, help="full-domain <stamp>.npy files (4, Z, Y, X) per time step")
     src.add_argument("--from_hr", type=str, help="an existing tree whose *_HR.npy files give the LR files")
     p.add_argument("--out_dir", type=str, default=None, help="root of the tree to write (default: --from_hr)")
@@ -57,14 +74,33 @@ def parse_args(argv=None):
     p.add_argument("--dz", type=float, default=5.0, help="level spacing (m)")
     p.add_argument("--hr_margin", type=int, default=40)
     p.add_argument("--time_sample_interval", type=int, default=2)
+    p.add_argument("--target_datetime", type=str, default=None,
+                   help="UTC datetime of the run under --root_result_dir, e.g. 2015-07-31T05:00:00")
+    p.add_argument("--discarded_initial_period", type=int, default=10, help="--grads_dir: time steps dropped")
+    p.add_argument("--min_index_height", type=int, default=4, help="--grads_dir: first level kept (17.5 m)")
+    p.add_argument("--num_levels", type=int, default=40, help="--grads_dir: levels kept")
+    p.add_argument("--nest_level", type=str, default="0n", help="--grads_dir: atmos_<nest_level>_<var>.ctl")
     p.add_argument("--device", type=str, default="cuda")
     a = p.parse_args(argv)
+    if (a.root_result_dir is None) != (a.target_datetime is None):
+        p.error("--root_result_dir and --target_datetime go together")
+    if a.root_result_dir is not None:
+        from sr3d_amd.src.io_grads import get_grads_dir_micro_meteorology
+        try:
+            dt = datetime.datetime.strptime(a.target_datetime, "%Y-%m-%dT%H:%M:%S")
+        except ValueError:
+            p.error("--target_datetime must look like 2015-07-31T05:00:00")
+        a.grads_dir = str(get_grads_dir_micro_meteorology(pathlib.Path(a.root_result_dir), dt))
+    if a.grads_dir is not None and (a.discarded_initial_period < 0 or a.min_index_height < 0 or a.num_levels <= 0
+                                    or a.num_levels % SR_SCALE):
+        p.error(f"--discarded_initial_period / --min_index_height must be >= 0, --num_levels a positive multiple "
+                f"of {SR_SCALE}")
     if a.out_dir is None:
         if a.from_hr is None:
-            p.error("--out_dir is required with --raw_dir")
+            p.error("--out_dir is required with --raw_dir and --grads_dir")
         a.out_dir = a.from_hr
-    if a.raw_dir is not None and a.hr_building_path is None:
-        p.error("--hr_building_path is required with --raw_dir")
+    if a.from_hr is None and a.hr_building_path is None:
+        p.error("--hr_building_path is required with --raw_dir and --grads_dir")
     if a.hr_margin <= 0 or a.hr_margin % SR_SCALE:
         p.error(f"--hr_margin must be a positive multiple of {SR_SCALE}")
     if a.time_sample_interval < 1:
@@ -154,6 +190,49 @@ def run_raw(a):
         save(lr_file, lr.cpu().numpy())
 
 
+def run_grads(a):
+    import torch
+    from sr3d_amd import ops
+    from sr3d_amd.src.building_height_helper import calc_is_in_building
+    from sr3d_amd.src.training_data_maker import _load_atmos_data, lr_building_tops
+
+    data = _load_atmos_data(a.grads_dir, min_index_height=a.min_index_height,
+                            max_index_height=a.min_index_height + a.num_levels, margin=0,
+                            discarded_initial_period=a.discarded_initial_period, nest_level=a.nest_level)
+    T, Z, Y, X = data.shape
+    if T == 0 or Z != a.num_levels:
+        raise ValueError(f"{a.grads_dir}: {T} time steps and {Z} levels after the selection "
+                         f"(--discarded_initial_period {a.discarded_initial_period}, levels "
+                         f"[{a.min_index_height}, {a.min_index_height + a.num_levels}))")
+    steps = sample_times(range(T), a.time_sample_interval)
+    stamps = [t.astype("datetime64[s]").astype(datetime.datetime) for t in data.time]
+    dev = torch.device(a.device)
+    hr_tz, hr_ez = building_yx(a.hr_building_path, "Tz"), building_yx(a.hr_building_path, "Ez")
+    lr_tz, lr_ez = building_yx(a.lr_building_path, "Tz"), building_yx(a.lr_building_path, "Ez")
+    assert (Y, X) == hr_tz.shape and (Y // SR_SCALE, X // SR_SCALE) == lr_tz.shape
+    m, ml = a.hr_margin, a.hr_margin // SR_SCALE
+    group = pathlib.Path(a.out_dir) / a.data_group
+    levs = np.asarray(data.lev, dtype=np.float64)
+
+    # the first kept time step fixes the HR mask
+    _, tm_nan = data.step(steps[0], dev, want_tm_mask=True)
+    hm = (calc_is_in_building(hr_tz, hr_ez, levs) + tm_nan.cpu().numpy().astype(float)) > 0
+    save(group / "hr_is_in_build.npy", _tile(hm)[..., m:-m, m:-m])
+    lz = calc_is_in_building(lr_tz, lr_ez, levs[::SR_SCALE])
+    save(group / "lr_is_in_build.npy", _tile(lz)[..., ml:-ml, ml:-ml])
+    hr_mask = torch.from_numpy(hm).to(dev)
+    tops = torch.from_numpy(lr_building_tops(lr_tz, lr_ez, levs, SR_SCALE)).to(dev)
+
+    todo = [i for i in steps if not all(f.exists() for f in out_paths(a.out_dir, a.data_group, stamps[i]))]
+    # the copy to the device and the decode of step k + 1 run on a side stream while step k is coarse-grained
+    for i, raw in data.steps(todo, dev):
+        hr, lr = ops.coarse_grain_outside_buildings(raw, hr_mask, tops, scale=SR_SCALE, hr_margin=m, lev=levs,
+                                                    align_nan=True)
+        hr_file, lr_file = out_paths(a.out_dir, a.data_group, stamps[i])
+        save(hr_file, hr.cpu().numpy())
+        save(lr_file, lr.cpu().numpy())
+
+
 def run_from_hr(a):
     import torch
     from sr3d_amd import ops
@@ -189,7 +268,9 @@ def main(argv=None):
     logging.basicConfig(level=logging.INFO, format="%(message)s", stream=sys.stdout)
     a = parse_args(argv)
     import sr3d_amd  # noqa: F401  (loads the engine before any work)
-    if a.raw_dir is not None:
+    if a.grads_dir is not None:
+        run_grads(a)
+    elif a.raw_dir is not None:
         run_raw(a)
     else:
         run_from_hr(a)

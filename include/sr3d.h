@@ -349,6 +349,31 @@ typedef struct {
 size_t sr3d_lrdata_workspace_bytes(int C, int Y, int X);
 int sr3d_lrdata(const sr3d_lrdata_params_t* params, void* workspace, size_t workspace_bytes, void* stream);
 
+/* One time step of the LES's GrADS output, decoded on the device (reference datascience/: io_grads.read_xarray +
+ * align_nan_grids, without xgrads / xarray): four variables (tm, vl, vp, vr), each given as the raw bytes of the
+ * step's level window exactly as they lie in the data file.  Variable v, output level z, row y, column x reads the
+ * 4-byte word at
+ *   src[v] + level_offset[v] + (zrev ? Z-1-z : z) * level_pitch[v] + ((yrev ? Y-1-y : y) * X + x) * 4
+ * (level_pitch carries the two 4-byte record markers of `options sequential`), swaps its bytes if `byteswap`,
+ * compares it as fp32 with (float)undef[v] (numpy's `da == ds.undef` on a float32 array): equal -> NaN, a NaN in the
+ * file stays NaN; with align_nan, variables 1..3 are NaN wherever variable 0 is.  out: (4, Z, Y, X) fp32 dense, bit
+ * identical to that numpy expression; tm_is_nan (optional): (Z, Y, X) uint8, 1 where out[0] is NaN.
+ * 16-byte loads and stores when X % 4 == 0 and every slab base and pitch keeps 16-byte alignment, 4-byte ones
+ * otherwise.  One launch on `stream`, no host synchronisation, no workspace. */
+typedef struct {
+  int32_t X, Y, Z;
+  int32_t byteswap;           /* the file's byte order is not the host's (little endian) */
+  int32_t yrev, zrev;         /* the file stores rows / levels in descending order */
+  int32_t align_nan;
+  long long level_offset[4];  /* bytes from src[v] to the first value of file level 0; a multiple of 4 */
+  long long level_pitch[4];   /* bytes between level slabs, >= Y * X * 4; a multiple of 4 */
+  long long src_bytes[4];     /* size of src[v]: level_offset + (Z-1) * level_pitch + Y * X * 4 must fit */
+  double undef[4];
+  void* out;
+  void* tm_is_nan;            /* or NULL */
+} sr3d_grads_params_t;
+int sr3d_grads_decode(const void* const src[4], const sr3d_grads_params_t* params, void* stream);
+
 /* SSIM3D (reference src/ssim.py:52-115: masked structural similarity with a w x w x w Gaussian or uniform window,
  * zero padding).  img1, img2: (B, C, Z, Y, X); mask: (B, Cm, Z, Y, X) with Cm = 1 or C; `window`: the n 1-D taps
  * (HOST array, n odd, <= 15) whose triple outer product is the reference's 3-D window; mean_out: 1 float (device) =
