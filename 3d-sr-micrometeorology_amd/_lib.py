@@ -109,6 +109,8 @@ SYMBOLS = {
     "sr3d_lrdata_workspace_bytes": (_SZ, [_I, _I, _I]),
     "sr3d_lrdata": (_I, [C.POINTER(LrDataParams), _P, _SZ, _P]),
     "sr3d_grads_decode": (_I, [C.POINTER(C.c_void_p), C.POINTER(GradsParams), _P]),
+    "sr3d_interp_baseline_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I, _I]),
+    "sr3d_interp_baseline": (_I, [_P, _LL, _LL, _I, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),
     "sr3d_ssim3d_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I]),
     "sr3d_ssim3d": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, C.POINTER(_F), _I, _F, _F, _P, _P, _P, _P]),
     "sr3d_adam_step": (_I, [_P, _P, _P, _P, _LL, _D, _D, _D, _D, _I, _D, _P]),

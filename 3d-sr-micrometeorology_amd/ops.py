@@ -854,6 +854,63 @@ def coarse_grain_outside_buildings(raw: torch.Tensor, hr_mask: torch.Tensor, lr_
     return hr, lr
 
 
+# ---------------------------------------------------------------- interpolation baseline (the notebooks' fill_na)
+INTERP_SCALES = (2, 4)
+
+
+def interp_baseline(lr: torch.Tensor, lr_is_in_build: torch.Tensor, scale: int = 4,
+                    out: Optional[torch.Tensor] = None):
+    """the reference notebooks' ``fill_na`` on the GPU: ``lr`` (B, C, z, y, x) fp32 (NaN allowed; each (z, y, x) volume
+    dense, any batch / channel stride) is upsampled trilinearly x ``scale`` (2 or 4), blanked where ``lr_is_in_build``
+    (z, y, x; bool, uint8 or float, non-zero = inside a building) says so, and the blanks are filled linearly along z,
+    then y, then x (include/sr3d.h: sr3d_interp_baseline).  Forward only.  Returns (hr (B, C, s*z, s*y, s*x) fp32,
+    n_unfilled: 0-dim int32 on the device, the cells still NaN); ``out``: write into this dense tensor instead."""
+    what = "interp_baseline"
+    if torch.is_grad_enabled() and lr.requires_grad:
+        raise NotImplementedError(f"{what} has no backward on this engine: call it under torch.no_grad()")
+    if not lr.is_cuda:
+        raise RuntimeError(f"{what}: lr must live on the GPU: the sr3d engine has no CPU path")
+    if lr.dim() != 5:
+        raise ValueError(f"{what}: lr must be (B, C, z, y, x) (got {tuple(lr.shape)})")
+    if lr.dtype != torch.float32:
+        raise TypeError(f"{what}: lr must be float32 (got {lr.dtype})")
+    if scale not in INTERP_SCALES:
+        raise ValueError(f"{what}: scale {scale}: only {INTERP_SCALES} are implemented")
+    lr = lr.detach()
+    B, Cn, z, y, x = lr.shape
+    if min(B, Cn, z, y, x) <= 0:
+        raise ValueError(f"{what}: empty lr {tuple(lr.shape)}")
+    if tuple(lr.stride()[2:]) != (y * x, x, 1) or (Cn > 1 and lr.stride(1) < z * y * x) or (
+            B > 1 and lr.stride(0) < z * y * x):
+        raise ValueError(f"{what}: every (z, y, x) volume of lr must be dense (strides {lr.stride()})")
+    if tuple(lr_is_in_build.shape) != (z, y, x):
+        raise ValueError(f"{what}: lr_is_in_build must be (z, y, x) = {(z, y, x)} (got {tuple(lr_is_in_build.shape)})")
+    if lr_is_in_build.device != lr.device:
+        raise ValueError(f"{what}: lr and lr_is_in_build must be on one device")
+    if lr_is_in_build.dtype == torch.bool:
+        mask = lr_is_in_build.contiguous().view(torch.uint8)
+    elif lr_is_in_build.dtype == torch.uint8:
+        mask = lr_is_in_build.contiguous()
+    else:
+        mask = (lr_is_in_build != 0).to(torch.uint8)
+    shape = (B, Cn, scale * z, scale * y, scale * x)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=lr.device)
+    elif tuple(out.shape) != shape or out.device != lr.device:
+        raise ValueError(f"{what}: out must be {shape} on {lr.device} (got {tuple(out.shape)} on {out.device})")
+    count = torch.empty(1, dtype=torch.int32, device=lr.device)
+    ws = torch.empty(max(1, L.lib.sr3d_interp_baseline_workspace_bytes(B, Cn, z, y, x, scale)), dtype=torch.uint8,
+                     device=lr.device)
+    with torch.cuda.device(lr.device):
+        L.check(L.lib.sr3d_interp_baseline(C.c_void_p(lr.data_ptr()), lr.stride(0), lr.stride(1), L.DTYPE_F32, B, Cn, z,
+                                           y, x, L.dev_ptr(mask, f"{what}: lr_is_in_build", dtype=torch.uint8), z, y,
+                                           x, scale, L.dev_ptr(out, f"{what}: out"),
+                                           L.dev_ptr(count, f"{what}: count", dtype=torch.int32),
+                                           C.c_void_p(ws.data_ptr()), ws.numel(), L.stream_ptr()),
+                "sr3d_interp_baseline")
+    return out, count[0]
+
+
 # ---------------------------------------------------------------- GrADS decode (the LES's raw output -> fields)
 def _four(v, cast, what: str):
     vals = [cast(x) for x in v] if isinstance(v, (list, tuple)) else [cast(v)] * 4

@@ -374,6 +374,30 @@ typedef struct {
 } sr3d_grads_params_t;
 int sr3d_grads_decode(const void* const src[4], const sr3d_grads_params_t* params, void* stream);
 
+/* The interpolation baseline of the reference's plotting notebooks (`fill_na`, pytorch/notebook/plot_horizontal_
+ * sections_at_various_locations.ipynb and plot_horizontal_vertical_section_at_fixed_location.ipynb, cell "Define
+ * methods"): lr (B, C, z, y, x) fp32, sample b / channel c at lr + b * batch_stride + c * channel_stride floats, each
+ * (z, y, x) volume dense, NaN allowed; lr_is_in_build (mz, my, mx) uint8, which must be the LR grid, shared by every
+ * sample and channel; scale s = 2 or 4.
+ *   1. F.interpolate(mode="trilinear", align_corners=False, scale_factor=s): per axis src = max(0, (dst + 0.5) / s -
+ *      0.5), i0 = floor(src), i1 = min(i0 + 1, n - 1), l1 = src - i0, l0 = 1 - l1; the value is wz0 * (wy0 * (wx0 *
+ *      v000 + wx1 * v001) + wy1 * (..)) + wz1 * (..) in fp32, each w0 * a + w1 * b evaluated as fma(a, w0, fl(w1 * b))
+ *      and nothing else contracted: the rounding of ATen's CPU kernel for contiguous tensors;
+ *   2. a cell is NaN where lr_is_in_build[z / s][y / s][x / s] != 0 (a NaN of step 1 stays);
+ *   3. along z, then y, then x, each pass on the result of the one before: a line with k NaN cells out of n is left
+ *      alone if k == 0 or k >= n - 1; otherwise each NaN cell i becomes float((double(y_hi) - double(y_lo)) / (hi - lo)
+ *      * (i - lo) + double(y_lo)), (lo, hi) the valid cells around i, or the two nearest valid cells past an end
+ *      (scipy interp1d(kind="linear", fill_value="extrapolate") on index coordinates).  Valid cells are never rewritten.
+ * out: (B, C, s*z, s*y, s*x) fp32 dense (16-byte stores when s*x % 4 == 0 and out is 16-byte aligned, 4-byte stores
+ * otherwise); n_unfilled: one int32 (DEVICE) = the number of cells still NaN at the end.  dtype must be
+ * SR3D_DTYPE_F32; lr, out, n_unfilled and workspace must be 4-byte aligned.  Five launches on `stream` (two that zero
+ * the flags and the count, the column pass, the y and x fills), no host synchronisation; results do not depend on
+ * scheduling. */
+size_t sr3d_interp_baseline_workspace_bytes(int B, int C, int z, int y, int x, int scale);
+int sr3d_interp_baseline(const void* lr, long long batch_stride, long long channel_stride, int dtype, int B, int C,
+                         int z, int y, int x, const void* lr_is_in_build, int mz, int my, int mx, int scale, void* out,
+                         void* n_unfilled, void* workspace, size_t workspace_bytes, void* stream);
+
 /* SSIM3D (reference src/ssim.py:52-115: masked structural similarity with a w x w x w Gaussian or uniform window,
  * zero padding).  img1, img2: (B, C, Z, Y, X); mask: (B, Cm, Z, Y, X) with Cm = 1 or C; `window`: the n 1-D taps
  * (HOST array, n odd, <= 15) whose triple outer product is the reference's 3-D window; mean_out: 1 float (device) =
