@@ -29,6 +29,16 @@ EVAL_INDEX = {"L1": 0, "L2": 1, "MaskedL1": 2, "MaskedL2": 3, "MaskedL1NearWall"
               "AbsDiffTemperatureLev": 10, "DiffVelocityNormLev": 11, "AbsDiffDivergence": 12, "DiffOmegaNorm": 13}
 EVAL_SUMS = {"abs": 14, "mask_abs": 15, "sq": 16, "mask_sq": 17, "mask": 18}
 EVAL_COUNT = 19
+# rows of the outputs of sr3d_eval_level_profiles (include/sr3d.h: SR3D_PROFILE_*, SR3D_PROFILE_SUM_*)
+PROFILE_INDEX = {"L1": 0, "L2": 1, "MaskedL1": 2, "MaskedL2": 3, "MaskedL1NearWall": 4, "MaskedL2NearWall": 5,
+                 "ResidualContinuity": 6, "ResidualContinuityTarget": 7, "AbsDiffTemperature": 8,
+                 "DiffVelocityNorm": 9, "AbsDiffDivergence": 10, "DiffOmegaNorm": 11, "ChannelwiseMseT": 12,
+                 "ChannelwiseMseU": 13, "ChannelwiseMseV": 14, "ChannelwiseMseW": 15}
+PROFILE_COUNT = 16
+PROFILE_SUM_INDEX = {"abs": 0, "sq": 1, "sq_T": 2, "sq_U": 3, "sq_V": 4, "sq_W": 5, "mask": 6, "mask_abs": 7,
+                     "mask_sq": 8, "near": 9, "near_abs": 10, "near_sq": 11, "mask_dT": 12, "mask_dV": 13,
+                     "mask_int": 14, "near_int": 15, "res_p": 16, "res_t": 17, "ddiv": 18, "omega": 19}
+PROFILE_SUM_COUNT = 20
 ROTATE_COEF_READY, ROTATE_PHYSICAL = 1, 2   # flags of the rotation calls (include/sr3d.h: SR3D_ROTATE_*)
 
 
@@ -97,7 +107,9 @@ SYMBOLS = {
     "sr3d_weighted_lp_bwd": (_I, [_P, _P, _P, _I, _I, _LL, _I, _P, _P, _P]),
     "sr3d_eval_metrics_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
     "sr3d_eval_metrics": (_I, [_P, _P, _P, _I, _I, _I, _I, C.POINTER(_F), _F, _I, _P, _P, _P]),
-    "sr3d_rotate_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I]),
+    "sr3d_eval_level_profiles_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "sr3d_eval_level_profiles": (_I, [_P, _P, _P, _I, _I, _I, _I, C.POINTER(_F), _F, _I, _P, _P, _P, _P]),
+    "sr3d_rotate_workspace_bytes":(_SZ, [_I, _I, _I, _I, _I]),
     "sr3d_rotate_fields": (_I, [_P, _P, _I, _I, _I, _I, _I, C.POINTER(_D), C.POINTER(_D), _D, _I, _P, _SZ, _P]),
     "sr3d_rotate_building": (_I, [_P, _P, _I, _I, _I, _I, _I, _D, _D, _I, _P, _SZ, _P]),
     "sr3d_equivariance_errors": (_I, [_P, _P, _I, _I, _I, _I, C.POINTER(_D), C.POINTER(_D), _D, _I, _I, _I, _I, _I, _P,

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 
@@ -573,6 +573,31 @@ def eval_metrics(p: torch.Tensor, t: torch.Tensor, b: torch.Tensor, stds: Sequen
     _eval_cache.update(refs=tuple(weakref.ref(x) for x in (p0, t0, b0)), meta=meta,
                        stds=[w if w is not None else float("nan") for w in want], out=out)
     return out
+
+
+def eval_level_profiles(p: torch.Tensor, t: torch.Tensor, b: torch.Tensor, stds: Sequence[Optional[float]],
+                        delta: float = 5.0, per_sample: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Every evaluation metric PER LEVEL from one fused pass (include/sr3d.h: sr3d_eval_level_profiles): returns
+    ``(values, sums)`` on the device, ``values`` (PROFILE_COUNT, Z) indexed with ``_lib.PROFILE_INDEX`` and ``sums``
+    (PROFILE_SUM_COUNT, Z) with ``_lib.PROFILE_SUM_INDEX``; with ``per_sample`` both get a leading batch dimension.
+    Row ``AbsDiffTemperature`` / ``DiffVelocityNorm`` at level k is the reference's module with ``lev=k``.
+
+    ``stds`` = (std_T, std_u, std_v, std_w); a None entry counts as 1.0.  Nothing is cached: every call launches."""
+    p, t, b = p.detach().contiguous(), t.detach().contiguous(), b.detach().contiguous()
+    if p.dim() != 5 or p.shape[1] != 4 or t.shape != p.shape or tuple(b.shape) != (p.shape[0], 1) + tuple(p.shape[2:]):
+        raise ValueError("eval_level_profiles expects p, t: (B,4,Z,Y,X) and masks: (B,1,Z,Y,X)")
+    if len(stds) != 4:
+        raise ValueError("eval_level_profiles expects stds = (std_T, std_u, std_v, std_w)")
+    B, _, Z, Y, X = p.shape
+    lead = (B,) if per_sample else ()
+    ws = torch.empty(L.lib.sr3d_eval_level_profiles_workspace_bytes(B, Z, Y, X) // 4, dtype=torch.float32,
+                     device=p.device)
+    sums, values = _empty(lead + (L.PROFILE_SUM_COUNT, Z), p), _empty(lead + (L.PROFILE_COUNT, Z), p)
+    sc = (C.c_float * 4)(*[1.0 if v is None else float(v) for v in stds])
+    L.check(L.lib.sr3d_eval_level_profiles(L.dev_ptr(p), L.dev_ptr(t), L.dev_ptr(b), B, Z, Y, X, sc, float(delta),
+                                           int(bool(per_sample)), L.dev_ptr(sums), L.dev_ptr(values), L.dev_ptr(ws),
+                                           L.stream_ptr()), "sr3d_eval_level_profiles")
+    return values, sums
 
 
 def ssim3d(img1: torch.Tensor, img2: torch.Tensor, mask: torch.Tensor, window: Sequence[float], max_val: float = 1.0,

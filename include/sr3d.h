@@ -259,6 +259,62 @@ size_t sr3d_eval_metrics_workspace_bytes(int B, int Z, int Y, int X);
 int sr3d_eval_metrics(const void* p, const void* t, const void* b, int B, int Z, int Y, int X, const float stds[4],
                       float delta_meter, int lev, void* out, void* workspace, void* stream);
 
+/* ---- height-resolved evaluation: every metric per level from ONE pass ------------ */
+/* The formulas of the evaluation modules above restricted to z == k in numerator and denominator alike, for every
+ * level k at once (csrc/sr3d_eval_profile.hip): ABS_DIFF_TEMPERATURE / DIFF_VELOCITY_NORM at level k are exactly the
+ * reference's AbsDiffTemperature(lev=k) / DiffVelocityVectorNorm(lev=k).  Same inputs as sr3d_eval_metrics.
+ * per_sample == 0: sums_out is (SR3D_PROFILE_SUM_COUNT, Z) and values_out (SR3D_PROFILE_COUNT, Z), over the whole
+ * batch (what the reference's modules see); per_sample != 0: (B, ., Z), one profile per sample, bit-equal to B
+ * one-sample calls.  Both in DEVICE memory, fp32 (sums rounded from double totals).  The interior profiles
+ * (RESIDUAL_CONTINUITY .. , ABS_DIFF_DIVERGENCE, DIFF_OMEGA_NORM) divide by sum_int b - sum_int near without eps:
+ * NaN where a level has no such voxel, always at levels 0 and Z-1.  No atomics: two calls are bit-equal. */
+enum {
+  SR3D_PROFILE_SUM_ABS = 0,        /* sum |d| over the 4 channels (d = p - t) */
+  SR3D_PROFILE_SUM_SQ = 1,         /* sum d^2 over the 4 channels */
+  SR3D_PROFILE_SUM_SQ_T = 2,       /* sum d^2 of channel T; U, V, W follow at 3, 4, 5 */
+  SR3D_PROFILE_SUM_SQ_U = 3,
+  SR3D_PROFILE_SUM_SQ_V = 4,
+  SR3D_PROFILE_SUM_SQ_W = 5,
+  SR3D_PROFILE_SUM_MASK = 6,       /* sum b */
+  SR3D_PROFILE_SUM_MASK_ABS = 7,   /* sum b |d| */
+  SR3D_PROFILE_SUM_MASK_SQ = 8,    /* sum b d^2 */
+  SR3D_PROFILE_SUM_NEAR = 9,       /* sum near (near-wall flag of the mask) */
+  SR3D_PROFILE_SUM_NEAR_ABS = 10,
+  SR3D_PROFILE_SUM_NEAR_SQ = 11,
+  SR3D_PROFILE_SUM_MASK_DT = 12,   /* sum b |d_T| std_T */
+  SR3D_PROFILE_SUM_MASK_DV = 13,   /* sum b || std_v d_v || */
+  SR3D_PROFILE_SUM_MASK_INT = 14,  /* on the interior (1 <= z, y, x <= n - 2), M = b (1 - near): sum b */
+  SR3D_PROFILE_SUM_NEAR_INT = 15,  /* sum near */
+  SR3D_PROFILE_SUM_RES_P = 16,     /* sum |M div p| */
+  SR3D_PROFILE_SUM_RES_T = 17,     /* sum |M div t| */
+  SR3D_PROFILE_SUM_DDIV = 18,      /* sum |M div p - M div t| */
+  SR3D_PROFILE_SUM_OMEGA = 19,     /* sum || M omega(p) - M omega(t) || */
+  SR3D_PROFILE_SUM_COUNT = 20
+};
+enum {
+  SR3D_PROFILE_L1 = 0,             /* over 4 B Y X */
+  SR3D_PROFILE_L2 = 1,
+  SR3D_PROFILE_MASKED_L1 = 2,      /* / (4 sum b + 1e-30) */
+  SR3D_PROFILE_MASKED_L2 = 3,
+  SR3D_PROFILE_MASKED_L1_NEAR_WALL = 4,   /* / (4 sum near + 1e-30) */
+  SR3D_PROFILE_MASKED_L2_NEAR_WALL = 5,
+  SR3D_PROFILE_RESIDUAL_CONTINUITY = 6,   /* / (sum_int b - sum_int near) */
+  SR3D_PROFILE_RESIDUAL_CONTINUITY_TARGET = 7,
+  SR3D_PROFILE_ABS_DIFF_TEMPERATURE = 8,  /* / (sum b + 1e-30) */
+  SR3D_PROFILE_DIFF_VELOCITY_NORM = 9,
+  SR3D_PROFILE_ABS_DIFF_DIVERGENCE = 10,
+  SR3D_PROFILE_DIFF_OMEGA_NORM = 11,
+  SR3D_PROFILE_CHANNELWISE_MSE_T = 12,    /* over B Y X; U, V, W follow at 13, 14, 15 */
+  SR3D_PROFILE_CHANNELWISE_MSE_U = 13,
+  SR3D_PROFILE_CHANNELWISE_MSE_V = 14,
+  SR3D_PROFILE_CHANNELWISE_MSE_W = 15,
+  SR3D_PROFILE_COUNT = 16
+};
+size_t sr3d_eval_level_profiles_workspace_bytes(int B, int Z, int Y, int X);
+int sr3d_eval_level_profiles(const void* p, const void* t, const void* b, int B, int Z, int Y, int X,
+                             const float stds[4], float delta_meter, int per_sample, void* sums_out, void* values_out,
+                             void* workspace, void* stream);
+
 /* Rotation about the vertical axis (reference src/equivariance_error_calculator.py): every (y, x) plane of an NCDHW
  * fp32 tensor rotated as scipy.ndimage.rotate(a, angle_deg, axes=(-2, -1), reshape=False) does it -- cubic B-spline
  * (prefilter with the mirror boundary, fp64 coefficients), mode 'constant', cval = 0.  angle_deg is reduced modulo
