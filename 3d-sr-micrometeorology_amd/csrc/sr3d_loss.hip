@@ -95,7 +95,7 @@ struct MixParams {
 
 __device__ __forceinline__ float cdiff(float hi, float lo, float w) { return hi * w + lo * (-w); }
 
-// Pass 1 as a 2.5-D marching stencil (the layout of csrc/sr3d_eval.hip): a workgroup owns a column of the grid, 8 rows
+// Pass 1 as a 2.5-D marching stencil (the layout of csrc/sr3d_eval_march.h): a workgroup owns a column of the grid, 8 rows
 // x 62 columns x 16 planes, and walks it plane by plane.  x neighbours: wave shuffles (one row = one wave, lanes 0 and
 // 63 are halo columns, every load is one contiguous 256-byte row segment); y neighbours: an LDS tile [field][10 rows][64]
 // (waves 0 and 9 are halo rows; double-buffered by plane parity, one barrier per plane); z neighbours: a rolling 3-plane

@@ -116,6 +116,48 @@ def test_agrees_with_the_whole_volume_pass(eng, ragged, kind):
     assert checked == 12
 
 
+def test_exact_inputs_pin_both_passes_to_each_other_bit_for_bit(eng):
+    """on inputs where every fp32 operation of the non-interior terms is exact, the order of summation cannot matter:
+    the whole-volume pass and the per-level pass, which share their stencil and term formulas
+    (csrc/sr3d_eval_march.h) and differ in how they add up, must agree bit for bit, and with the fp64 restatement.
+    Fields are multiples of 1/4 in [0, 2) that differ in T and u only (|d| < 2, sqrt(dv^2) = |dv|), scales are powers
+    of two: every term is a multiple of 1/16 of at most 4; a block adds at most 8 * 62 * 16 * 4 = 31744 of them and
+    the whole case 2 * 18 * 11 * 70 * 4 = 110880, so every partial sum is an integer below 2^24 in units of 1/16."""
+    L = eng._lib
+    B, Z, Y, X = 2, 18, 11, 70           # two tiles on every axis, the second one partial
+    stds, delta = (2.0, 1.0, 4.0, 0.5), 4.0
+    g = torch.Generator().manual_seed(61)
+    t = torch.randint(0, 8, (B, 4, Z, Y, X), generator=g).float() / 4
+    p = t.clone()
+    p[:, :2] = torch.randint(0, 8, (B, 2, Z, Y, X), generator=g).float() / 4
+    b = (torch.rand(B, 1, Z, Y, X, generator=g) > 0.02).float()     # sparse: about half the open cells are not near a wall
+    b[:, :, :7, 3:8, 20:40] = 0          # a built block: near-wall cells on its faces and roof
+    interior = ("res_p", "res_t", "ddiv", "omega")      # divergence / vorticity terms are not exactly representable
+    _, S = LR.level_profiles_ref(p.double(), t.double(), b.double(), stds, delta)
+    for name in LR.SUMS:
+        if name not in interior:
+            units = torch.cat([S[name], S[name].sum()[None]]) * 16
+            assert torch.equal(units, units.round()) and float(units.max()) < 2 ** 24, name
+    assert 0.25 * float(S["mask_int"].sum()) < float(S["near_int"].sum()) < 0.75 * float(S["mask_int"].sum())
+
+    pd, td, bd = p.to(DEV), t.to(DEV), b.to(DEV)
+    values, sums = eng.ops.eval_level_profiles(pd, td, bd, stds, delta=delta)
+    per_lev = torch.stack([eng.ops.eval_metrics(pd, td, bd, stds, delta, k) for k in range(Z)]).cpu()
+    values, sums = values.cpu(), sums.cpu()
+    for name, i in L.PROFILE_SUM_INDEX.items():
+        if name in interior:
+            assert_rows_close(sums, S, {name: i}, "exact")
+        else:
+            assert torch.equal(sums[i].double(), S[name]), name
+    for name, i in L.EVAL_SUMS.items():
+        total = sums[L.PROFILE_SUM_INDEX[name]].double().sum().float()
+        for k in range(Z):
+            assert torch.equal(bits(total), bits(per_lev[k, i])), (name, k)
+    for prof, entry in (("AbsDiffTemperature", "AbsDiffTemperatureLev"), ("DiffVelocityNorm", "DiffVelocityNormLev")):
+        got, ref = values[L.PROFILE_INDEX[prof]], per_lev[:, L.EVAL_INDEX[entry]]
+        assert bool((got > 0).all()) and torch.equal(bits(got), bits(ref)), prof
+
+
 def test_podium_case(eng):
     """two built levels under open air: which levels are empty, exactly zero or NaN is known in advance"""
     L = eng._lib
