@@ -273,6 +273,8 @@ class GatedConv3dAct(torch.autograd.Function):
         """``dual``: return the output TWICE (the same storage): for an output with two consumers -- the next block and the
         U-Net's skip connection -- backward then receives the two gradients separately and adds them inside
         ``sr3d_gated_act_bwd_sum`` instead of autograd adding them in an elementwise pass of its own"""
+        # (as in Conv3dAct: sources that deferred their activation backward to THIS layer's input gradient)
+        ctx.src_boxes = [getattr(s, "_sr3d_act_box", None) for s in srcs]
         srcs = [s.contiguous() for s in srcs]
         B, cin, (Z, Y, X) = _check_srcs(srcs)
         cout = int(w_feat.shape[0])
@@ -330,7 +332,7 @@ class GatedConv3dAct(torch.autograd.Function):
         dxs, dw, (dbf, dbg) = _grads_two_streams(
             desc, srcs, needs, [d_feat, d_gate], w_feat, w_gate, want_w,
             [d_feat if (ctx.has_bf and ctx.needs_input_grad[2]) else None, d_gate if ctx.needs_input_grad[3] else None],
-            ctx.x_amax, dy_amax)
+            ctx.x_amax, dy_amax, ctx.src_boxes)
         dwf, dwg = (dw[:desc.Cout], dw[desc.Cout:]) if dw is not None else (None, None)
         return (dwf, dwg, dbf, dbg, None, None, None, *dxs)
 

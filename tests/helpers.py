@@ -37,6 +37,28 @@ def relerr(a, b):
     return num / den if den > 0 else num
 
 
+def rep(t):
+    """round to bf16-representable values, keep fp32 storage"""
+    return t.to(torch.bfloat16).float()
+
+
+def q(t):
+    """what storing as bf16 does to an fp64 result"""
+    return t.float().to(torch.bfloat16).double()
+
+
+def within_one_ulp(got, ref, what):
+    """a bf16 result against the fp64 result rounded once to bf16 (tests/test_gpu_bf16.py: exactness per op)"""
+    got, ref = got.detach().float().cpu().double(), ref.double()
+    err = (got - ref).abs()
+    # one bf16 ulp of the element, plus the fp32 accumulation noise of the sum behind it (relative to the tensor's scale,
+    # not to an element that happens to cancel to ~0)
+    tol = 2.0 ** -7 * ref.abs() + 1e-5 * float(ref.pow(2).mean().sqrt())
+    bad = int((err > tol).sum())
+    assert bad == 0, (what, bad, float((err / tol).max()))
+    assert relerr(got, ref) < 2e-4, (what, relerr(got, ref))
+
+
 def tower_mask(Z, Y, X):
     """deterministic 'buildings': boxes rising from z=0 (1 = fluid, 0 = building); same as oracle/make_golden.py"""
     b = torch.ones(1, 1, Z, Y, X)

@@ -23,7 +23,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from helpers import cfg_of, load_golden, relerr, sub, synthetic_inputs, T
+from helpers import cfg_of, load_golden, q, relerr, rep, sub, synthetic_inputs, T, within_one_ulp
 from oracle import ref_cpu as R
 
 pytestmark = pytest.mark.gpu
@@ -36,27 +36,6 @@ def eng():
     assert torch.cuda.is_available(), "GPU tests need a GPU"
     import sr3d_amd
     return sr3d_amd
-
-
-def rep(t):
-    """round to bf16-representable values, keep fp32 storage"""
-    return t.to(BF).float()
-
-
-def q(t):
-    """what storing as bf16 does to an fp64 result"""
-    return t.float().to(BF).double()
-
-
-def within_one_ulp(got, ref, what):
-    got, ref = got.detach().float().cpu().double(), ref.double()
-    err = (got - ref).abs()
-    # one bf16 ulp of the element, plus the fp32 accumulation noise of the sum behind it (relative to the tensor's scale,
-    # not to an element that happens to cancel to ~0)
-    tol = 2.0 ** -7 * ref.abs() + 1e-5 * float(ref.pow(2).mean().sqrt())
-    bad = int((err > tol).sum())
-    assert bad == 0, (what, bad, float((err / tol).max()))
-    assert relerr(got, ref) < 2e-4, (what, relerr(got, ref))
 
 
 def make_case(cs, cout, grid, seed, batch=2, wscale=0.05):
