@@ -39,6 +39,15 @@ PROFILE_SUM_INDEX = {"abs": 0, "sq": 1, "sq_T": 2, "sq_U": 3, "sq_V": 4, "sq_W":
                      "mask_sq": 8, "near": 9, "near_abs": 10, "near_sq": 11, "mask_dT": 12, "mask_dV": 13,
                      "mask_int": 14, "near_int": 15, "res_p": 16, "res_t": 17, "ddiv": 18, "omega": 19}
 PROFILE_SUM_COUNT = 20
+# rows of the outputs of sr3d_eval_wall_distance_profiles (include/sr3d.h: SR3D_WALLDIST_*, SR3D_WALLDIST_SUM_*): the
+# per-level names; the NEAR sums are POS ([b > 0]) here, and the cell count of a bin follows
+WALLDIST_INDEX = dict(PROFILE_INDEX)
+WALLDIST_COUNT = 16
+WALLDIST_SUM_INDEX = {**{{"near": "pos", "near_abs": "pos_abs", "near_sq": "pos_sq"}.get(k, k): v
+                         for k, v in PROFILE_SUM_INDEX.items()}, "cells": 20}
+WALLDIST_SUM_COUNT = 21
+WALLDIST_MAX_D = 30     # SR3D_WALLDIST_MAX_D
+WALL_DISTANCE_MAX_CAP = 254
 ROTATE_COEF_READY, ROTATE_PHYSICAL = 1, 2   # flags of the rotation calls (include/sr3d.h: SR3D_ROTATE_*)
 
 
@@ -109,6 +118,10 @@ SYMBOLS = {
     "sr3d_eval_metrics": (_I, [_P, _P, _P, _I, _I, _I, _I, C.POINTER(_F), _F, _I, _P, _P, _P]),
     "sr3d_eval_level_profiles_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
     "sr3d_eval_level_profiles": (_I, [_P, _P, _P, _I, _I, _I, _I, C.POINTER(_F), _F, _I, _P, _P, _P, _P]),
+    "sr3d_wall_distance_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "sr3d_wall_distance": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "sr3d_eval_wall_distance_profiles_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I]),
+    "sr3d_eval_wall_distance_profiles": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, C.POINTER(_F), _F, _I, _P, _P, _P, _P]),
     "sr3d_rotate_workspace_bytes":(_SZ, [_I, _I, _I, _I, _I]),
     "sr3d_rotate_fields": (_I, [_P, _P, _I, _I, _I, _I, _I, C.POINTER(_D), C.POINTER(_D), _D, _I, _P, _SZ, _P]),
     "sr3d_rotate_building": (_I, [_P, _P, _I, _I, _I, _I, _I, _D, _D, _I, _P, _SZ, _P]),

@@ -1,6 +1,7 @@
 // The 2.5-D marching stencil of the evaluation passes (gfx950): one walk over (p, t, b) that hands every voxel's error
-// terms, plane by plane, to a sink.  sr3d_eval.hip adds them up over the whole volume, sr3d_eval_profile.hip per level;
-// the stencil, the rounding rules and the formula of every term exist here and nowhere else.
+// terms, plane by plane, to a sink.  sr3d_eval.hip adds them up over the whole volume, sr3d_eval_profile.hip per level,
+// sr3d_walldist.hip per class of distance from the walls; the stencil, the rounding rules and the formula of every term
+// exist here and nowhere else.
 //
 //   d = p - t (4 channels: T, u, v, w);  near = calc_mask_near_build_wall(b) (loss_maker.py:57-83)
 //   interior = voxels 1 .. n-2 in z, y, x;  M = b * (1 - near) there (loss_maker.py:84-113, 133-160)
@@ -72,6 +73,32 @@ __device__ __forceinline__ float cdiff(float hi, float lo, float w) {
   return a + b;
 }
 
+// A thread's place in the launch (block (x: march_blocks, y: sample), kMarchThreads threads): the integer decoding the
+// march starts from, also for a sink that reads a further volume at its voxel.
+struct MarchPlace {
+  int lane, row;        // row 0 / MROWS-1: halo rows
+  int x, y, tiz, bi;    // the thread's column, its z tile and its sample
+  bool in_xy;
+  bool row_reports;     // wave-uniform
+  bool owner;           // this thread's voxels have terms
+};
+__device__ __forceinline__ MarchPlace march_place(const MarchInputs& q) {
+  MarchPlace at;
+  at.lane = threadIdx.x & 63, at.row = threadIdx.x >> 6;
+  int blk = blockIdx.x;
+  const int ntx = (q.X + MX - 1) / MX, nty = (q.Y + MY - 1) / MY;
+  const int tix = blk % ntx;
+  blk /= ntx;
+  const int tiy = blk % nty;
+  at.tiz = blk / nty;
+  at.bi = blockIdx.y;
+  at.x = tix * MX - 1 + at.lane, at.y = tiy * MY - 1 + at.row;
+  at.in_xy = (unsigned)at.x < (unsigned)q.X && (unsigned)at.y < (unsigned)q.Y;
+  at.row_reports = at.row >= 1 && at.row <= MY;
+  at.owner = at.in_xy && at.lane >= 1 && at.lane <= MX && at.row_reports;
+  return at;
+}
+
 // The march of one workgroup (kMarchThreads threads, block (x: march_blocks, y: sample)) over its column; `tile` is the
 // calling kernel's LDS.  The column holds the planes tiz * MZS .. of z tile tiz (so j % MZS is a plane's index within
 // its column); the march returns how many.  For every plane j of the column, in rising order, v[kP] holds the terms of
@@ -86,19 +113,10 @@ __device__ __forceinline__ float cdiff(float hi, float lo, float w) {
 template <typename Sink>
 __device__ __forceinline__ int eval_march(const MarchInputs& q, float (*tile)[MF][MROWS][64], Sink& sink) {
 #pragma clang fp contract(off)
-  const int lane = threadIdx.x & 63, row = threadIdx.x >> 6;          // row 0 / MROWS-1: halo rows
-  int blk = blockIdx.x;
-  const int ntx = (q.X + MX - 1) / MX, nty = (q.Y + MY - 1) / MY;
-  const int tix = blk % ntx;
-  blk /= ntx;
-  const int tiy = blk % nty;
-  const int tiz = blk / nty;
-  const int bi = blockIdx.y;
-  const int x = tix * MX - 1 + lane, y = tiy * MY - 1 + row;
+  const MarchPlace at = march_place(q);
+  const int lane = at.lane, row = at.row, tiz = at.tiz, bi = at.bi, x = at.x, y = at.y;
   const int z_lo = tiz * MZS, z_hi = min(z_lo + MZS, q.Z);             // output planes [z_lo, z_hi)
-  const bool in_xy = (unsigned)x < (unsigned)q.X && (unsigned)y < (unsigned)q.Y;
-  const bool row_reports = row >= 1 && row <= MY;                      // wave-uniform
-  const bool owner = in_xy && lane >= 1 && lane <= MX && row_reports;  // this thread's voxels have terms
+  const bool in_xy = at.in_xy, row_reports = at.row_reports, owner = at.owner;
   const bool inner_xy = owner && x >= 1 && x < q.X - 1 && y >= 1 && y < q.Y - 1;
   const long long zyx = (long long)q.Z * q.Y * q.X, sz = (long long)q.Y * q.X;
   const long long col = (long long)y * q.X + x;

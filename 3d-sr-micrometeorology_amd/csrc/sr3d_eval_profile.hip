@@ -5,7 +5,7 @@
 //
 //   eval_profile_kernel   a block owns an (MY x MX x MZS) column.  For each reported plane every thread has kP = 20
 //                         terms (its one voxel of that plane); a row's wave reduces them with an exchange reduction
-//                         (below: 22 shuffles for all 20 sums, not 20 x 6) and 20 lanes store the row's sums to LDS
+//                         (sr3d_wave_reduce.h: 22 shuffles for all 20 sums, not 20 x 6) and 20 lanes store the row's sums to LDS
 //                         [row][plane][acc].  After the march the MY rows are added in fixed order and [plane][acc]
 //                         goes to the workspace at [sample][z tile][xy tile][plane][acc].
 //   eval_profile_final    one block per (level, sample-or-batch): the partials of all (x, y) tiles of that level,
@@ -14,49 +14,17 @@
 // No floating-point atomics; every order of summation is fixed by the indices alone: two calls are bit-equal, and a
 // per-sample result is bit-equal to a one-sample call.
 #include "sr3d_eval_march.h"
+#include "sr3d_wave_reduce.h"
 
 namespace {
 
-static_assert(kP == 20, "the exchange reduction below is laid out for 20 sums");
+static_assert(kP == 20, "the exchange reduction is laid out for 20 sums");
 
 struct ProfParams : MarchInputs {
   float* part;    // [B][z tiles][xy tiles][MZS][kP]
   float* sums;    // ([B],) kP, Z
   float* values;  // ([B],) SR3D_PROFILE_COUNT, Z
 };
-
-// ---- exchange reduction: N sums over the 64 lanes of a wave ---------------------------------------------------------
-// One step pairs lane l with lane l ^ O: the lane whose bit O is clear keeps the lower half of the values, the other
-// one the upper half, and each sends the half it drops.  N values -> ceil(N / 2) per step (20 -> 10 -> 5 -> 3 -> 2 ->
-// 1), then the two lanes that hold the same value add up: 10 + 5 + 3 + 2 + 1 + 1 = 22 shuffles for all 20 sums.
-template <int N, int O>
-__device__ __forceinline__ void exchange_step(float* v, int lane) {
-  constexpr int H = (N + 1) / 2;
-  const bool up = (lane & O) != 0;
-#pragma unroll
-  for (int i = 0; i < H; i++) {
-    const float lo = v[i], hi = (i + H < N) ? v[i + H] : 0.f;
-    const float keep = up ? hi : lo, send = up ? lo : hi;
-    v[i] = keep + __shfl_xor(send, O, 64);
-  }
-}
-
-// after wave_reduce20, v[0] of an even lane with reduce20_slot(lane) >= 0 is the wave's sum of that slot
-__device__ __forceinline__ void wave_reduce20(float* v, int lane) {
-  exchange_step<20, 32>(v, lane);
-  exchange_step<10, 16>(v, lane);
-  exchange_step<5, 8>(v, lane);
-  exchange_step<3, 4>(v, lane);
-  exchange_step<2, 2>(v, lane);
-  v[0] += __shfl_xor(v[0], 1, 64);
-}
-
-__device__ __forceinline__ int reduce20_slot(int lane) {
-  const int s3 = ((lane >> 2) & 1) * 2 + ((lane >> 1) & 1);    // of 3 (slot 3 is padding)
-  const int s5 = ((lane >> 3) & 1) * 3 + s3;                   // of 5 (slot 5 is padding)
-  if ((lane & 1) || s3 >= 3 || s5 >= 5) return -1;
-  return ((lane >> 5) & 1) * 10 + ((lane >> 4) & 1) * 5 + s5;
-}
 
 constexpr int kFinalThreads = 256, kFinalSlots = kFinalThreads / 32;
 

@@ -433,15 +433,44 @@ def avgpool2(b: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def near_wall_mask(b: torch.Tensor) -> torch.Tensor:
-    """calc_mask_near_build_wall (reference loss_maker.py:57-83)."""
+def _mask_dims(b: torch.Tensor, who: str):
+    if b.dim() != 5 or b.shape[1] != 1:
+        raise ValueError(f"{who} expects a (B,1,Z,Y,X) mask")
+    return b.shape[0], b.shape[2], b.shape[3], b.shape[4]
+
+
+def wall_distance(b: torch.Tensor, cap: int = 8) -> torch.Tensor:
+    """Chebyshev distance of every cell to the nearest built cell (``1 - b > 0``) of its sample, as a uint8 tensor
+    shaped like ``b``: 0 on built cells, ``min(distance, cap + 1)`` elsewhere (include/sr3d.h: sr3d_wall_distance;
+    ``1 <= cap <= 254``).  ``(dist <= n) & (b > 0)`` is the reference's near-wall mask of width n for every n <= cap."""
     b = b.detach().contiguous()
-    B, c, Z, Y, X = b.shape
-    if c != 1:
-        raise ValueError("near_wall_mask expects a (B,1,Z,Y,X) mask")
-    out = torch.empty_like(b)
-    L.check(L.lib.sr3d_near_wall(L.dev_ptr(b), L.dev_ptr(out), B, Z, Y, X, L.stream_ptr()), "sr3d_near_wall")
+    B, Z, Y, X = _mask_dims(b, "wall_distance")
+    out = torch.empty(b.shape, dtype=torch.uint8, device=b.device)
+    ws = torch.empty(L.lib.sr3d_wall_distance_workspace_bytes(B, Z, Y, X), dtype=torch.uint8, device=b.device)
+    L.check(L.lib.sr3d_wall_distance(L.dev_ptr(b), L.dev_ptr(out, "dist", torch.uint8), B, Z, Y, X, int(cap),
+                                     L.dev_ptr(ws, "workspace", torch.uint8), L.stream_ptr()), "sr3d_wall_distance")
     return out
+
+
+def near_wall_mask(b: torch.Tensor, num_filter_applications: int = 1) -> torch.Tensor:
+    """calc_mask_near_build_wall (reference loss_maker.py:57-83).  One filter application is the 27-tap kernel; n of
+    them are a Chebyshev dilation by n cells, read off one distance transform: ``(dist <= n) & (b > 0)``."""
+    n = int(num_filter_applications)
+    if n < 1:
+        raise ValueError("near_wall_mask: num_filter_applications must be >= 1")
+    b = b.detach().contiguous()
+    B, Z, Y, X = _mask_dims(b, "near_wall_mask")
+    if n == 1:
+        out = torch.empty_like(b)
+        L.check(L.lib.sr3d_near_wall(L.dev_ptr(b), L.dev_ptr(out), B, Z, Y, X, L.stream_ptr()), "sr3d_near_wall")
+        return out
+    if n > L.WALL_DISTANCE_MAX_CAP:
+        # no two cells of the grid are farther apart than max(Z, Y, X) - 1 <= 254: every wider mask equals this one
+        if max(Z, Y, X) > L.WALL_DISTANCE_MAX_CAP + 1:
+            raise NotImplementedError(f"near_wall_mask: num_filter_applications > {L.WALL_DISTANCE_MAX_CAP} needs a "
+                                      f"grid of at most {L.WALL_DISTANCE_MAX_CAP + 1} cells per axis")
+        n = L.WALL_DISTANCE_MAX_CAP
+    return ((wall_distance(b, n) <= n) & (b > 0)).to(torch.float32)
 
 
 def preprocess(x: torch.Tensor, means: Sequence[float], stds: Sequence[float], scaling: Optional[float] = None,
@@ -599,6 +628,44 @@ def eval_level_profiles(p: torch.Tensor, t: torch.Tensor, b: torch.Tensor, stds:
     L.check(L.lib.sr3d_eval_level_profiles(L.dev_ptr(p), L.dev_ptr(t), L.dev_ptr(b), B, Z, Y, X, sc, float(delta),
                                            int(bool(per_sample)), L.dev_ptr(sums), L.dev_ptr(values), L.dev_ptr(ws),
                                            L.stream_ptr()), "sr3d_eval_level_profiles")
+    return values, sums
+
+
+def eval_wall_distance_profiles(p: torch.Tensor, t: torch.Tensor, b: torch.Tensor, stds: Sequence[Optional[float]],
+                                delta_meter: float = 5.0, max_distance: int = 8, dist: Optional[torch.Tensor] = None
+                                ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Every evaluation metric PER CLASS OF DISTANCE FROM THE WALLS from one fused pass (include/sr3d.h:
+    sr3d_eval_wall_distance_profiles): returns ``(values, sums)`` on the device, ``values`` (WALLDIST_COUNT, D + 2)
+    indexed with ``_lib.WALLDIST_INDEX`` and ``sums`` (WALLDIST_SUM_COUNT, D + 2) with ``_lib.WALLDIST_SUM_INDEX``, D =
+    ``max_distance`` (1 .. 30).  Bin 0 holds the built cells, bin k the cells at Chebyshev distance k, bin D + 1 the
+    cells farther than D.  Rows ``MaskedL1NearWall`` / ``MaskedL2NearWall`` are cumulative: at bin k they are the
+    reference's modules with ``num_filter_applications=k``.
+
+    ``dist`` = ``wall_distance(b, cap)`` with ``cap >= max_distance``, computed here when not given (a caller that
+    scores several predictions on one mask passes it).  ``stds`` as in ``eval_level_profiles``."""
+    p, t, b = p.detach().contiguous(), t.detach().contiguous(), b.detach().contiguous()
+    if p.dim() != 5 or p.shape[1] != 4 or t.shape != p.shape or tuple(b.shape) != (p.shape[0], 1) + tuple(p.shape[2:]):
+        raise ValueError("eval_wall_distance_profiles expects p, t: (B,4,Z,Y,X) and masks: (B,1,Z,Y,X)")
+    if len(stds) != 4:
+        raise ValueError("eval_wall_distance_profiles expects stds = (std_T, std_u, std_v, std_w)")
+    D = int(max_distance)
+    if not 1 <= D <= L.WALLDIST_MAX_D:
+        raise ValueError(f"eval_wall_distance_profiles: max_distance must be in 1 .. {L.WALLDIST_MAX_D}")
+    if dist is None:
+        dist = wall_distance(b, D)
+    elif dist.dtype != torch.uint8 or dist.shape != b.shape:
+        raise ValueError("eval_wall_distance_profiles expects dist: uint8, shaped like the mask (ops.wall_distance)")
+    dist = dist.detach().contiguous()
+    B, _, Z, Y, X = p.shape
+    ws = torch.empty(L.lib.sr3d_eval_wall_distance_profiles_workspace_bytes(B, Z, Y, X, D) // 8, dtype=torch.float64,
+                     device=p.device)
+    sums, values = _empty((L.WALLDIST_SUM_COUNT, D + 2), p), _empty((L.WALLDIST_COUNT, D + 2), p)
+    sc = (C.c_float * 4)(*[1.0 if v is None else float(v) for v in stds])
+    L.check(L.lib.sr3d_eval_wall_distance_profiles(L.dev_ptr(p), L.dev_ptr(t), L.dev_ptr(b),
+                                                   L.dev_ptr(dist, "dist", torch.uint8), B, Z, Y, X, sc,
+                                                   float(delta_meter), D, L.dev_ptr(sums), L.dev_ptr(values),
+                                                   L.dev_ptr(ws, "workspace", torch.float64), L.stream_ptr()),
+            "sr3d_eval_wall_distance_profiles")
     return values, sums
 
 

@@ -44,11 +44,9 @@ def make_loss(config: dict) -> nn.Module:
 
 
 def calc_mask_near_build_wall(building: torch.Tensor, num_filter_applications: int = 1) -> torch.Tensor:
-    """loss_maker.py:57-83 (one filter application, the only value the reference uses)."""
+    """loss_maker.py:57-83; n filter applications are a Chebyshev dilation by n cells (``ops.wall_distance``)."""
     assert len(building.shape) == 5
-    if num_filter_applications != 1:
-        raise NotImplementedError("num_filter_applications != 1")
-    return ops.near_wall_mask(building)
+    return ops.near_wall_mask(building, num_filter_applications)
 
 
 class MyL1Loss(nn.Module):
@@ -231,13 +229,24 @@ class MaskedL1LossNearWall(_FusedMetric):
     def __init__(self, eps: float = 1e-30, num_filter_applications: int = 1):
         super().__init__()
         _check_eps(eps)
-        if num_filter_applications != 1:
-            raise NotImplementedError("num_filter_applications != 1")
-        self.eps, self.num_filter_applications = eps, num_filter_applications
+        if int(num_filter_applications) != num_filter_applications or num_filter_applications < 1:
+            raise ValueError("num_filter_applications must be a whole number >= 1")
+        self.eps, self.num_filter_applications = eps, int(num_filter_applications)
+
+    def forward(self, predicts: torch.Tensor, targets: torch.Tensor, masks: torch.Tensor):
+        if self.num_filter_applications == 1:
+            return super().forward(predicts, targets, masks)
+        # sum(near_n |d|^k) / (4 sum(near_n) + eps) is the masked loss with near_n in the mask's place
+        near = ops.near_wall_mask(masks, self.num_filter_applications)
+        out = ops.eval_metrics(predicts, targets, near, self._stds(), self.delta_meter, self._lev())
+        return out[EVAL_INDEX[self._wide_entry]]
+
+    _wide_entry = "MaskedL1"
 
 
 class MaskedL2LossNearWall(MaskedL1LossNearWall):
     entry = "MaskedL2NearWall"
+    _wide_entry = "MaskedL2"
 
 
 class _VelocityMetric(_FusedMetric):

@@ -315,6 +315,75 @@ int sr3d_eval_level_profiles(const void* p, const void* t, const void* b, int B,
                              const float stds[4], float delta_meter, int per_sample, void* sums_out, void* values_out,
                              void* workspace, void* stream);
 
+/* ---- wall-distance-resolved evaluation (csrc/sr3d_walldist.hip) ------------------ */
+/* Chebyshev distance to the nearest built cell.  b: (B,1,Z,Y,X) fp32; dist_out: (B,1,Z,Y,X) UINT8; 1 <= cap <= 254.
+ * A cell with 1.0f - b > 0 gets 0, every other cell min(distance to the nearest such cell of the same sample, cap + 1);
+ * nothing is built outside the grid, and a sample with nothing built is cap + 1 everywhere.  The reference's
+ * calc_mask_near_build_wall(b, num_filter_applications = n) (loss_maker.py:57-83: n box filters, then > 0) is
+ * (dist <= n) & (b > 0) for every n <= cap.  Three launches (one per axis) for any cap; workspace: one byte per voxel. */
+size_t sr3d_wall_distance_workspace_bytes(int B, int Z, int Y, int X);
+int sr3d_wall_distance(const void* b, void* dist_out, int B, int Z, int Y, int X, int cap, void* workspace,
+                       void* stream);
+
+/* Every metric of the evaluation PER DISTANCE CLASS from one pass of the marching stencil.  Same inputs as
+ * sr3d_eval_level_profiles plus dist (uint8, made by sr3d_wall_distance with cap >= D), 1 <= D <= 30, whole batch only.
+ * Bins: 0 is dist == 0, k = 1 .. D is dist == k, D + 1 is dist > D.  sums_out is (SR3D_WALLDIST_SUM_COUNT, D + 2) and
+ * values_out (SR3D_WALLDIST_COUNT, D + 2), fp32 in DEVICE memory, rounded from double totals.  The values are the
+ * formulas of SR3D_PROFILE_* restricted to the bin in numerator and denominator alike, except:
+ *   L1, L2 divide by 4 CELLS and CHANNELWISE_MSE_* by CELLS (an empty bin gives NaN);
+ *   MASKED_L1/L2_NEAR_WALL at bin k are CUMULATIVE: sum_{j<=k} POS_ABS / (4 sum_{j<=k} POS + 1e-30), which is the
+ *   reference's MaskedL1LossNearWall(num_filter_applications = k) for k = 1 .. D;
+ *   the interior rows keep M = b (1 - near_1) and are NaN where a bin has no such voxel (bins 0 and 1 of a binary mask).
+ * No atomics: two calls are bit-equal. */
+enum {
+  SR3D_WALLDIST_SUM_ABS = 0,        /* 0 .. 8 and 12 .. 19: as SR3D_PROFILE_SUM_*, over the voxels of the bin */
+  SR3D_WALLDIST_SUM_SQ = 1,
+  SR3D_WALLDIST_SUM_SQ_T = 2,
+  SR3D_WALLDIST_SUM_SQ_U = 3,
+  SR3D_WALLDIST_SUM_SQ_V = 4,
+  SR3D_WALLDIST_SUM_SQ_W = 5,
+  SR3D_WALLDIST_SUM_MASK = 6,
+  SR3D_WALLDIST_SUM_MASK_ABS = 7,
+  SR3D_WALLDIST_SUM_MASK_SQ = 8,
+  SR3D_WALLDIST_SUM_POS = 9,        /* sum [b > 0]: the cells the reference's near-wall flag can select */
+  SR3D_WALLDIST_SUM_POS_ABS = 10,   /* sum [b > 0] |d| */
+  SR3D_WALLDIST_SUM_POS_SQ = 11,    /* sum [b > 0] d^2 */
+  SR3D_WALLDIST_SUM_MASK_DT = 12,
+  SR3D_WALLDIST_SUM_MASK_DV = 13,
+  SR3D_WALLDIST_SUM_MASK_INT = 14,
+  SR3D_WALLDIST_SUM_NEAR_INT = 15,
+  SR3D_WALLDIST_SUM_RES_P = 16,
+  SR3D_WALLDIST_SUM_RES_T = 17,
+  SR3D_WALLDIST_SUM_DDIV = 18,
+  SR3D_WALLDIST_SUM_OMEGA = 19,
+  SR3D_WALLDIST_SUM_CELLS = 20,     /* voxels of the bin */
+  SR3D_WALLDIST_SUM_COUNT = 21
+};
+enum {
+  SR3D_WALLDIST_L1 = 0,             /* over 4 CELLS */
+  SR3D_WALLDIST_L2 = 1,
+  SR3D_WALLDIST_MASKED_L1 = 2,
+  SR3D_WALLDIST_MASKED_L2 = 3,
+  SR3D_WALLDIST_MASKED_L1_NEAR_WALL = 4,   /* cumulative over the bins 0 .. k */
+  SR3D_WALLDIST_MASKED_L2_NEAR_WALL = 5,
+  SR3D_WALLDIST_RESIDUAL_CONTINUITY = 6,
+  SR3D_WALLDIST_RESIDUAL_CONTINUITY_TARGET = 7,
+  SR3D_WALLDIST_ABS_DIFF_TEMPERATURE = 8,
+  SR3D_WALLDIST_DIFF_VELOCITY_NORM = 9,
+  SR3D_WALLDIST_ABS_DIFF_DIVERGENCE = 10,
+  SR3D_WALLDIST_DIFF_OMEGA_NORM = 11,
+  SR3D_WALLDIST_CHANNELWISE_MSE_T = 12,    /* over CELLS; U, V, W follow at 13, 14, 15 */
+  SR3D_WALLDIST_CHANNELWISE_MSE_U = 13,
+  SR3D_WALLDIST_CHANNELWISE_MSE_V = 14,
+  SR3D_WALLDIST_CHANNELWISE_MSE_W = 15,
+  SR3D_WALLDIST_COUNT = 16
+};
+#define SR3D_WALLDIST_MAX_D 30
+size_t sr3d_eval_wall_distance_profiles_workspace_bytes(int B, int Z, int Y, int X, int D);
+int sr3d_eval_wall_distance_profiles(const void* p, const void* t, const void* b, const void* dist, int B, int Z, int Y,
+                                     int X, const float stds[4], float delta_meter, int D, void* sums_out,
+                                     void* values_out, void* workspace, void* stream);
+
 /* Rotation about the vertical axis (reference src/equivariance_error_calculator.py): every (y, x) plane of an NCDHW
  * fp32 tensor rotated as scipy.ndimage.rotate(a, angle_deg, axes=(-2, -1), reshape=False) does it -- cubic B-spline
  * (prefilter with the mirror boundary, fp64 coefficients), mode 'constant', cval = 0.  angle_deg is reduced modulo
