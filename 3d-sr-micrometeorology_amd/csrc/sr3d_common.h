@@ -201,6 +201,14 @@ struct SrProfScope {
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
+// Workgroup -> XCD remap.  Hardware deals block ids round-robin over the 8 XCDs, each with its own L2; this gives the ids
+// that are congruent mod 8 -- one XCD -- a run of consecutive virtual ids, so that neighbours in the kernel's own order
+// share an L2.  Bijective for any grid size.
+__device__ __forceinline__ int sr3d_xcd_remap(const int nwg, const int bid) {
+  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+}
+
 // Activations are stored as fp32 or as bfloat16 (sr3d_conv_desc_t.dtype).  Kernels that only move or reduce them, and
 // the fp32-MFMA fallback kernels, are templated on the STORAGE type and compute in fp32: bf16raw is the 16-bit pattern.
 typedef unsigned short bf16raw;

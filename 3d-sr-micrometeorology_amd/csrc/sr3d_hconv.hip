@@ -180,25 +180,15 @@ __global__ __launch_bounds__(HNT, (BF && HCONV_NWB_BF == 3) ? 3 : 2) void hconv_
   __builtin_assume(wave >= 0 && wave < HNT / 64);
 
   // workgroup -> (row block, voxel tile); the row blocks of one tile run next to each other on one XCD
-  int v;
-  {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
-  const int nblk = v % p.nblk;
-  int blk = v / p.nblk;
-  const int tix = blk % p.ntx;
-  blk /= p.ntx;
-  const int tiy = blk % p.nty;
-  const int tiz = blk / p.nty;
+  const int v = sr3d_xcd_remap(gridDim.x, blockIdx.x);
+  const SplitTile tile = split_tile_of(v, p.nblk, p.ntx, p.nty);
+  const int nblk = tile.nblk;
   const int b = blockIdx.y;
-  const int z0 = tiz * 2, y0 = tiy * 4, x0 = tix * 32;
+  const int z0 = tile.tiz * 2, y0 = tile.tiy * 4, x0 = tile.tix * 32;
   const long long ZYX = (long long)p.Z * p.Y * p.X;
   const int chan_bytes = (int)(ZYX * ESZ);
 
-  int sw = BF ? 0 : split_scale_exp(*p.absmax_w);
-  if (sw == kSplitScaleNone) sw = 0;
+  const int sw = BF ? 0 : split_scale_exp_or0(*p.absmax_w);
   // exchange slots for the wave maxima [chunk parity][wave]: in the padding behind the 816 voxels of halo plane 0
   float* xmax = reinterpret_cast<float*>(Hs + HVOX * 16);
 
@@ -239,33 +229,13 @@ __global__ __launch_bounds__(HNT, (BF && HCONV_NWB_BF == 3) ? 3 : 2) void hconv_
       swr2[r] = -1;
     }
   }
-  // Per-slice base pointers of this sample, pinned in scalar registers: left to itself hipcc turns the slice selects into
-  // dependent kernel-argument loads (two or three ~200-cycle scalar-load round trips per channel, in every wave, at the
-  // start of every chunk).
-  // (separate variables, not arrays: an array would be indexed in scratch memory)
-#define SR3D_SLICE_BASE(i) (reinterpret_cast<unsigned long long>(p.in.ptr[i]) + (unsigned long long)((long long)b * p.in.bstride[i]) * ESZ)
-  unsigned long long sb0 = SR3D_SLICE_BASE(0), sb1 = SR3D_SLICE_BASE(1), sb2 = SR3D_SLICE_BASE(2), sb3 = SR3D_SLICE_BASE(3);
-#undef SR3D_SLICE_BASE
-  int cb0 = p.in.cbeg[0], cb1 = p.in.cbeg[1], cb2 = p.in.cbeg[2], cb3 = p.in.cbeg[3];
-  split_pin_scalar(sb0), split_pin_scalar(sb1), split_pin_scalar(sb2), split_pin_scalar(sb3);
-  split_pin_scalar(cb0), split_pin_scalar(cb1), split_pin_scalar(cb2), split_pin_scalar(cb3);
-  auto slice_of = [&](const int gc) { return (gc >= cb1) + (gc >= cb2) + (gc >= cb3); };
-  // (mask arithmetic instead of selects: hipcc turns a select chain over four values into a lookup table in scratch)
-  unsigned long long dsb1 = sb1 - sb0, dsb2 = sb2 - sb1, dsb3 = sb3 - sb2;
-  int dcb1 = cb1 - cb0, dcb2 = cb2 - cb1, dcb3 = cb3 - cb2;
-  split_pin_scalar(dsb1), split_pin_scalar(dsb2), split_pin_scalar(dsb3), split_pin_scalar(dcb1), split_pin_scalar(dcb2), split_pin_scalar(dcb3);
-  auto chan_base = [&](const int gc) {   // gc is wave-uniform
-    const long long m1 = -(long long)(gc >= cb1), m2 = -(long long)(gc >= cb2), m3 = -(long long)(gc >= cb3);
-    const unsigned long long base = sb0 + (dsb1 & (unsigned long long)m1) + (dsb2 & (unsigned long long)m2) + (dsb3 & (unsigned long long)m3);
-    const int c0 = cb0 + (dcb1 & (int)m1) + (dcb2 & (int)m2) + (dcb3 & (int)m3);
-    return base + (unsigned long long)(unsigned)(gc - c0) * (unsigned long long)(unsigned)chan_bytes;
-  };
+  const SplitSliceBases<ESZ> sl(p.in, b, chan_bytes);   // per-slice base pointers of this sample
   float raw[NR][BQUAD ? 16 : 8 * RV];   // [round][channel][voxel of the quad]; bf16 quads: [round][channel][pair of the quad]
   // QUAD: channel c of this wave's 8, both rounds (two 16-byte loads per lane)
   auto load_raw_q = [&](const int chunk, const int c) {
     if constexpr (QUAD) {
       const int gc = chunk * HKC + sh * 8 + c;   // wave-uniform
-      const unsigned long long base = chan_base(gc < p.K ? gc : p.K - 1);
+      const unsigned long long base = sl.chan_base(gc < p.K ? gc : p.K - 1);
       const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, gc < p.K ? chan_bytes : 0, 0x00020000);
 #pragma unroll
       for (int r = 0; r < NR; r++) {
@@ -290,7 +260,7 @@ __global__ __launch_bounds__(HNT, (BF && HCONV_NWB_BF == 3) ? 3 : 2) void hconv_
 #pragma unroll
       for (int c = 0; c < 8; c++) {
         const int gc = chunk * HKC + sh * 8 + c;   // wave-uniform
-        const unsigned long long base = chan_base(gc < p.K ? gc : p.K - 1);
+        const unsigned long long base = sl.chan_base(gc < p.K ? gc : p.K - 1);
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, gc < p.K ? chan_bytes : 0, 0x00020000);
 #pragma unroll
         for (int r = 0; r < NR; r++) {
@@ -308,13 +278,13 @@ __global__ __launch_bounds__(HNT, (BF && HCONV_NWB_BF == 3) ? 3 : 2) void hconv_
     const int gc0 = chunk * HKC + sh * 8;      // wave-uniform
     const int first = gc0 < p.K ? gc0 : p.K - 1, last = gc0 + 7 < p.K ? gc0 + 7 : p.K - 1;
     unsigned long long cbase[8];
-    if (slice_of(first) == slice_of(last)) {   // the usual case: 8 consecutive channels of one tensor
-      const unsigned long long b0 = chan_base(first);
+    if (sl.slice_of(first) == sl.slice_of(last)) {   // the usual case: 8 consecutive channels of one tensor
+      const unsigned long long b0 = sl.chan_base(first);
 #pragma unroll
       for (int c = 0; c < 8; c++) cbase[c] = b0 + (unsigned long long)c * (unsigned)chan_bytes;
     } else {
 #pragma unroll
-      for (int c = 0; c < 8; c++) cbase[c] = chan_base(gc0 + c < p.K ? gc0 + c : p.K - 1);
+      for (int c = 0; c < 8; c++) cbase[c] = sl.chan_base(gc0 + c < p.K ? gc0 + c : p.K - 1);
     }
 #pragma unroll
     for (int c = 0; c < 8; c++) {
@@ -338,9 +308,8 @@ __global__ __launch_bounds__(HNT, (BF && HCONV_NWB_BF == 3) ? 3 : 2) void hconv_
   // same layer (sr3d_hwgrad.hip needs max |x| per slice; this kernel sees every element anyway).  Only the workgroups of
   // the first row block export.
   const bool export_max = !BF && p.amax_out != nullptr && nblk == 0;
-  float rmax0 = 0.f, rmax1 = 0.f, rmax2 = 0.f, rmax3 = 0.f;
+  SplitSliceMax rmax;
   auto publish_max = [&](const int parity, const int ck) {
-    if constexpr (BF) return;   // no scaling: bf16 has fp32's exponent range
     if constexpr ((HCONV_ABL & 128) != 0) {   // ablation: the loads are waited for and consumed, no arithmetic
 #pragma unroll
       for (int r = 0; r < NR; r++)
@@ -353,20 +322,13 @@ __global__ __launch_bounds__(HNT, (BF && HCONV_NWB_BF == 3) ? 3 : 2) void hconv_
     for (int r = 0; r < NR; r++)   // (QUAD: the outer quads bring up to three columns from beyond the halo: elements of the
 #pragma unroll                     //  same tensor, so the tile scale is only more cautious and the exported maxima stay exact)
       for (int c = 0; c < 8 * RV; c += 2) m = fmaxf(fmaxf(m, fabsf(raw[r][c])), fabsf(raw[r][c + 1]));
-    m = split_wave_max(m);
-    if (lane == 0) xmax[parity * 4 + wave] = m;
+    m = split_publish_max<BF>(xmax, parity, wave, lane, m);
     if (export_max) {
       const int gc0 = ck * HKC + sh * 8;
-      const int sa = slice_of(gc0 < p.K ? gc0 : p.K - 1), sb = slice_of(gc0 + 7 < p.K ? gc0 + 7 : p.K - 1);
-      auto credit = [&](const int sl, const float mv) {
-        rmax0 = sl == 0 ? fmaxf(rmax0, mv) : rmax0;
-        rmax1 = sl == 1 ? fmaxf(rmax1, mv) : rmax1;
-        rmax2 = sl == 2 ? fmaxf(rmax2, mv) : rmax2;
-        rmax3 = sl == 3 ? fmaxf(rmax3, mv) : rmax3;
-      };
-      if (sa == sb) {
-        credit(sa, m);
-      } else {   // the 8 channels straddle a slice boundary (rare: once or twice per layer): one maximum per channel
+      const int sa = sl.slice_of(gc0 < p.K ? gc0 : p.K - 1), sb = sl.slice_of(gc0 + 7 < p.K ? gc0 + 7 : p.K - 1);
+      int sl_last = sa;
+      float m_last = m;   // one slice: the wave's maximum is that slice's
+      if (sa != sb) {     // the 8 channels straddle a slice boundary (rare: once or twice per layer): one maximum per channel
 #pragma unroll
         for (int c = 0; c < 8; c++) {
           float mc = 0.f;
@@ -375,17 +337,12 @@ __global__ __launch_bounds__(HNT, (BF && HCONV_NWB_BF == 3) ? 3 : 2) void hconv_
 #pragma unroll
             for (int v = 0; v < RV; v++) mc = fmaxf(mc, fabsf(raw[r][c * RV + v]));
           mc = split_wave_max(mc);
-          credit(slice_of(gc0 + c < p.K ? gc0 + c : p.K - 1), mc);
+          const int sc = sl.slice_of(gc0 + c < p.K ? gc0 + c : p.K - 1);
+          if (c < 7) rmax.credit(sc, mc); else sl_last = sc, m_last = mc;
         }
       }
+      rmax.credit(sl_last, m_last);   // (one credit site for both cases: with two, hipcc keeps a second copy of the four selects in every publish)
     }
-  };
-  // running scale exponent: the largest chunk magnitude seen so far decides (kSplitScaleNone until a non-zero chunk came)
-  auto next_scale = [&](const int parity, const int s_run) {
-    if constexpr (BF) return 0;
-    const float m = fmaxf(fmaxf(xmax[parity * 4 + 0], xmax[parity * 4 + 1]), fmaxf(xmax[parity * 4 + 2], xmax[parity * 4 + 3]));
-    const int s_c = __builtin_amdgcn_readfirstlane(split_scale_exp(m));
-    return s_c < s_run ? s_c : s_run;
   };
   constexpr int NPC = (QUAD || BQUAD) ? NR * 4 : NR;   // 16-byte pieces a lane builds per chunk and part
   h8 chi[NPC], clo[BQUAD ? 1 : NPC];   // halo pieces of the next chunk, split (bf16 PAIR: the two voxels of the pair; QUAD / bf16 quads: [round][voxel])
@@ -546,7 +503,7 @@ __global__ __launch_bounds__(HNT, (BF && HCONV_NWB_BF == 3) ? 3 : 2) void hconv_
   publish_max(0, 0);
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
-  int s_run = next_scale(0, kSplitScaleNone);   // exponent of the scale the accumulators are in
+  int s_run = split_next_scale<BF>(xmax, 0, kSplitScaleNone);   // exponent of the scale the accumulators are in
   convert(ldexpf(1.f, s_run));
   write_halo(0);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -579,11 +536,11 @@ __global__ __launch_bounds__(HNT, (BF && HCONV_NWB_BF == 3) ? 3 : 2) void hconv_
       // instruction per MFMA, in its shadow) instead of in a block of ~200 in front of them.
       constexpr int QLOAD = 8, QPUB = 8, QCONV = 9;
       if (!(HCONV_ABL & 1) && !TAIL && QUAD && kzy == QCONV) {
-        s_next = next_scale((chunk + 1) & 1, s_run);
+        s_next = split_next_scale<BF>(xmax, (chunk + 1) & 1, s_run);
         in_mult_next = ldexpf(1.f, s_next);
       }
       if (!(HCONV_ABL & 1) && !TAIL && !QUAD && kzy == AHEAD + 1) {
-        s_next = next_scale((chunk + 1) & 1, s_run);
+        s_next = split_next_scale<BF>(xmax, (chunk + 1) & 1, s_run);
         convert(ldexpf(1.f, s_next));
         // bf16: straight into the OTHER halo buffer (nobody has read it since the previous chunk; the per-phase barriers
         // that follow publish it long before the next chunk's first fragment read)
@@ -789,13 +746,7 @@ __global__ __launch_bounds__(HNT, (BF && HCONV_NWB_BF == 3) ? 3 : 2) void hconv_
     }
   }
 
-  if (export_max && lane == 0) {   // (bits of a non-negative float order like unsigned integers)
-    unsigned* slot = p.amax_out + ((v / p.nblk) & 63);
-    if (rmax0 > 0.f) atomicMax(slot, __float_as_uint(rmax0));
-    if (rmax1 > 0.f) atomicMax(slot + 64, __float_as_uint(rmax1));
-    if (rmax2 > 0.f) atomicMax(slot + 128, __float_as_uint(rmax2));
-    if (rmax3 > 0.f) atomicMax(slot + 192, __float_as_uint(rmax3));
-  }
+  if (export_max && lane == 0) rmax.export_to(p.amax_out + ((v / p.nblk) & 63));
   // ------------------------------------------------------------------ epilogue (16 x 16 tiles: column = lane & 15 = voxel,
   // row = 4 (lane >> 4) + register)
   // (sign: the accumulators changed sign nchunks - 1 times)
@@ -1234,16 +1185,6 @@ int sr3d_absmax_launch(const float* x, long long n, unsigned* slot, hipStream_t 
   return SR3D_OK;
 }
 
-namespace {
-
-inline void row_split(int rows, int* n2, int* n1) {   // 64-row blocks, and one last block of <= 32 rows
-  const int nfull = rows / 64, rem = rows - nfull * 64;
-  *n2 = nfull + (rem > 32 ? 1 : 0);
-  *n1 = (rem > 0 && rem <= 32) ? 1 : 0;
-}
-
-}  // namespace
-
 // SR3D_SPLIT_F16: 0 = off (fp32 Winograd everywhere), 1 / unset = on where the launch fills the chip, 2 = on for every
 // eligible layer whatever its size (tests).  Read per call: tests and tools switch it at run time.
 int sr3d_hconv_mode() {
@@ -1254,7 +1195,7 @@ int sr3d_hconv_mode() {
 // header (64 bytes: max |w|) + region A (64-row blocks) + region B (one 32-row block)
 size_t sr3d_hconv_image_bytes(int rows, int K, bool bf) {
   int n2, n1;
-  row_split(rows, &n2, &n1);
+  split_row_split(rows, &n2, &n1);
   const size_t w2 = bf ? HGeo<2, true>::WPHASE : HGeo<2>::WPHASE, w1 = bf ? HGeo<1, true>::WPHASE : HGeo<1>::WPHASE;
   return 64 + (size_t)ceil_div(K, HKC) * HPH * ((size_t)n2 * w2 + (size_t)n1 * w1);
 }
@@ -1280,7 +1221,7 @@ int sr3d_hconv_pack(int kind, int Cout, int Cin, int rows, int K, const float* w
   for (int i = 0; i <= SR3D_MAX_SRC; i++) p.rbeg[i] = rbeg ? rbeg[i] : INT_MAX;
   for (int i = 0; i < SR3D_MAX_SRC; i++) p.cbeg[i] = cbeg ? cbeg[i] : 0;
   int n2, n1;
-  row_split(rows, &n2, &n1);
+  split_row_split(rows, &n2, &n1);
   _Float16* body = (_Float16*)((unsigned char*)image + 64);
   for (int region = 0; region < 2; region++) {
     p.nblk = region == 0 ? n2 : n1;
@@ -1345,7 +1286,7 @@ int sr3d_hconv_launch(SrHconvParams& p, const void* image, int B, bool bf, hipSt
   p.nchunks = ceil_div(p.K, HKC);
   p.itail = hconv_itail_host(p.K, bf) ? 1 : 0;   // (sr3d_hconv_pack asked the same question)
   int n2, n1;
-  row_split(p.N, &n2, &n1);
+  split_row_split(p.N, &n2, &n1);
   const long long nsp = (long long)p.ntz * p.nty * p.ntx;
   SR3D_CHECK(nsp * (n2 + n1) < (1ll << 31), SR3D_E_ARG, "split-f16 conv: grid too large");
   // wide halo loads: fp32 quads need X % 4 == 0 and 16-byte aligned tensors (then every channel row is), bf16 pairs even

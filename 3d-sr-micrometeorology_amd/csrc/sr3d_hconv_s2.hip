@@ -144,28 +144,18 @@ __global__ __launch_bounds__(HNT, (BF && MODE == 2 && RT == 2 && !QD) ? 2 : 3) v
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   __builtin_assume(wave >= 0 && wave < HNT / 64);
 
-  int v;
-  {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
-  const int nblk = v % p.nblk;
-  int blk = v / p.nblk;
-  const int tix = blk % p.ntx;
-  blk /= p.ntx;
-  const int tiy = blk % p.nty;
-  const int tiz = blk / p.nty;
+  const int v = sr3d_xcd_remap(gridDim.x, blockIdx.x);
+  const SplitTile tile = split_tile_of(v, p.nblk, p.ntx, p.nty);
+  const int nblk = tile.nblk;
   const int b = blockIdx.y;
   const int ocls = MODE == 2 ? (int)blockIdx.z : 0;                 // output parity class of this launch slice
   const int TZ = MODE == 2 ? p.cZ[ocls] : p.Z, TY = MODE == 2 ? p.cY[ocls] : p.Y, TX = MODE == 2 ? p.cX[ocls] : p.X;
-  const int z0 = tiz * 2, y0 = tiy * 4, x0 = tix * 32;
+  const int z0 = tile.tiz * 2, y0 = tile.tiy * 4, x0 = tile.tix * 32;
   if (z0 >= TZ || y0 >= TY || x0 >= TX) return;                     // (the grid is sized for the largest class)
   const long long IZYX = (long long)p.IZ * p.IY * p.IX;
   const int chan_bytes = (int)(IZYX * ESZ);
 
-  int sw = BF ? 0 : split_scale_exp(*p.absmax_w);
-  if (sw == kSplitScaleNone) sw = 0;
+  const int sw = BF ? 0 : split_scale_exp_or0(*p.absmax_w);
   float* xmax = reinterpret_cast<float*>(Hs + HVOX * 16);
 
   // ---- staging geometry (class-independent part): halo voxel of this lane in round r
@@ -218,22 +208,7 @@ __global__ __launch_bounds__(HNT, (BF && MODE == 2 && RT == 2 && !QD) ? 2 : 3) v
     }
   }
 
-  // per-slice base pointers in scalar registers, mask arithmetic (see sr3d_hconv.hip)
-#define SR3D_SLICE_BASE(i) (reinterpret_cast<unsigned long long>(p.in.ptr[i]) + (unsigned long long)((long long)b * p.in.bstride[i]) * ESZ)
-  unsigned long long sb0 = SR3D_SLICE_BASE(0), sb1 = SR3D_SLICE_BASE(1), sb2 = SR3D_SLICE_BASE(2), sb3 = SR3D_SLICE_BASE(3);
-#undef SR3D_SLICE_BASE
-  int cb0 = p.in.cbeg[0], cb1 = p.in.cbeg[1], cb2 = p.in.cbeg[2], cb3 = p.in.cbeg[3];
-  split_pin_scalar(sb0), split_pin_scalar(sb1), split_pin_scalar(sb2), split_pin_scalar(sb3);
-  split_pin_scalar(cb0), split_pin_scalar(cb1), split_pin_scalar(cb2), split_pin_scalar(cb3);
-  unsigned long long dsb1 = sb1 - sb0, dsb2 = sb2 - sb1, dsb3 = sb3 - sb2;
-  int dcb1 = cb1 - cb0, dcb2 = cb2 - cb1, dcb3 = cb3 - cb2;
-  split_pin_scalar(dsb1), split_pin_scalar(dsb2), split_pin_scalar(dsb3), split_pin_scalar(dcb1), split_pin_scalar(dcb2), split_pin_scalar(dcb3);
-  auto chan_base = [&](const int gc) {
-    const long long m1 = -(long long)(gc >= cb1), m2 = -(long long)(gc >= cb2), m3 = -(long long)(gc >= cb3);
-    const unsigned long long base = sb0 + (dsb1 & (unsigned long long)m1) + (dsb2 & (unsigned long long)m2) + (dsb3 & (unsigned long long)m3);
-    const int c0 = cb0 + (dcb1 & (int)m1) + (dcb2 & (int)m2) + (dcb3 & (int)m3);
-    return base + (unsigned long long)(unsigned)(gc - c0) * (unsigned long long)(unsigned)chan_bytes;
-  };
+  const SplitSliceBases<ESZ> sl(p.in, b, chan_bytes);   // per-slice base pointers of this sample
 
   // ---- chunk iteration space.  MODE 1: virtual chunk vc = class * cpc + cc (class = K-side parity).  MODE 2: vc = cc,
   // the tap structure comes from the launch's output class.
@@ -249,7 +224,7 @@ __global__ __launch_bounds__(HNT, (BF && MODE == 2 && RT == 2 && !QD) ? 2 : 3) v
 #pragma unroll
       for (int c = 0; c < 4; c++) {
         const int gc = cc_ * HKC + wave * 4 + c;   // wave-uniform
-        const unsigned long long base = chan_base(gc < p.K ? gc : p.K - 1);
+        const unsigned long long base = sl.chan_base(gc < p.K ? gc : p.K - 1);
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, live && gc < p.K ? chan_bytes : 0, 0x00020000);
 #pragma unroll
         for (int r = 0; r < QNR; r++) {
@@ -276,12 +251,12 @@ __global__ __launch_bounds__(HNT, (BF && MODE == 2 && RT == 2 && !QD) ? 2 : 3) v
     for (int r = 0; r < HNR; r++) so_r[r] = ((smask[r] >> kc) & 1u) ? sbase[r] + cdelta : 0xffffffffu;
     // channel bases: the usual case is 8 consecutive channels of one tensor
     const int first = gc0 < p.K ? gc0 : p.K - 1, last = gc0 + 7 < p.K ? gc0 + 7 : p.K - 1;
-    const bool one_slice = ((first >= cb1) + (first >= cb2) + (first >= cb3)) == ((last >= cb1) + (last >= cb2) + (last >= cb3));
-    const unsigned long long b0 = chan_base(first);
+    const bool one_slice = sl.slice_of(first) == sl.slice_of(last);
+    const unsigned long long b0 = sl.chan_base(first);
 #pragma unroll
     for (int c = 0; c < 8; c++) {
       const int gc = gc0 + c;
-      const unsigned long long base = one_slice ? b0 + (unsigned long long)c * (unsigned)chan_bytes : chan_base(gc < p.K ? gc : p.K - 1);
+      const unsigned long long base = one_slice ? b0 + (unsigned long long)c * (unsigned)chan_bytes : sl.chan_base(gc < p.K ? gc : p.K - 1);
       const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, live && gc < p.K ? chan_bytes : 0, 0x00020000);
 #pragma unroll
       for (int r = 0; r < HNR; r++) {
@@ -296,9 +271,8 @@ __global__ __launch_bounds__(HNT, (BF && MODE == 2 && RT == 2 && !QD) ? 2 : 3) v
   // per-slice maxima of |x| over this workgroup's halo tiles (forward, first row block): exported at the end for the
   // split-f16 weight gradient of the same layer, as sr3d_hconv.hip does (the 8 parity classes together see every element)
   const bool export_max = MODE == 1 && !BF && !QD && p.amax_out != nullptr && nblk == 0;
-  float rmax0 = 0.f, rmax1 = 0.f, rmax2 = 0.f, rmax3 = 0.f;
+  SplitSliceMax rmax;
   auto publish_max = [&](const int parity, const int cc_) {
-    if constexpr (BF) return;   // no scaling: bf16 has fp32's exponent range
     float m = 0.f;
     if constexpr (QD) {   // (the last quad of a row brings three columns from beyond the halo: the tile scale is only more cautious)
 #pragma unroll
@@ -311,39 +285,27 @@ __global__ __launch_bounds__(HNT, (BF && MODE == 2 && RT == 2 && !QD) ? 2 : 3) v
 #pragma unroll
         for (int c = 0; c < 8; c += 2) m = fmaxf(fmaxf(m, fabsf(raw[r][c])), fabsf(raw[r][c + 1]));
     }
-    m = split_wave_max(m);
-    if (lane == 0) xmax[parity * 4 + wave] = m;
+    m = split_publish_max<BF>(xmax, parity, wave, lane, m);
     if constexpr (MODE == 1 && !BF && !QD) {
       if (export_max) {
         const int gc0 = cc_ * HKC + sh * 8;
-        auto slice_of = [&](const int gc) { return (gc >= cb1) + (gc >= cb2) + (gc >= cb3); };
-        const int sa = slice_of(gc0 < p.K ? gc0 : p.K - 1), sb = slice_of(gc0 + 7 < p.K ? gc0 + 7 : p.K - 1);
-        auto credit = [&](const int sl, const float mv) {
-          rmax0 = sl == 0 ? fmaxf(rmax0, mv) : rmax0;
-          rmax1 = sl == 1 ? fmaxf(rmax1, mv) : rmax1;
-          rmax2 = sl == 2 ? fmaxf(rmax2, mv) : rmax2;
-          rmax3 = sl == 3 ? fmaxf(rmax3, mv) : rmax3;
-        };
-        if (sa == sb) {
-          credit(sa, m);
-        } else {   // the 8 channels straddle a slice boundary: one maximum per channel
+        const int sa = sl.slice_of(gc0 < p.K ? gc0 : p.K - 1), sb = sl.slice_of(gc0 + 7 < p.K ? gc0 + 7 : p.K - 1);
+        int sl_last = sa;
+        float m_last = m;   // one slice: the wave's maximum is that slice's
+        if (sa != sb) {     // the 8 channels straddle a slice boundary (rare: once or twice per layer): one maximum per channel
 #pragma unroll
           for (int c = 0; c < 8; c++) {
             float mc = 0.f;
 #pragma unroll
             for (int r = 0; r < HNR; r++) mc = fmaxf(mc, fabsf(raw[r][c]));
             mc = split_wave_max(mc);
-            credit(slice_of(gc0 + c < p.K ? gc0 + c : p.K - 1), mc);
+            const int sc = sl.slice_of(gc0 + c < p.K ? gc0 + c : p.K - 1);
+            if (c < 7) rmax.credit(sc, mc); else sl_last = sc, m_last = mc;
           }
         }
+        rmax.credit(sl_last, m_last);   // (one credit site for both cases, see sr3d_hconv.hip)
       }
     }
-  };
-  auto next_scale = [&](const int parity, const int s_run) {
-    if constexpr (BF) return 0;
-    const float m = fmaxf(fmaxf(xmax[parity * 4 + 0], xmax[parity * 4 + 1]), fmaxf(xmax[parity * 4 + 2], xmax[parity * 4 + 3]));
-    const int s_c = __builtin_amdgcn_readfirstlane(split_scale_exp(m));
-    return s_c < s_run ? s_c : s_run;
   };
   auto split_and_write = [&](const float in_mult) {
     if constexpr (QD && BF) {   // the same half pieces, packed instead of split: (ch 0 | ch 1), (ch 2 | ch 3) of voxel v
@@ -435,7 +397,7 @@ __global__ __launch_bounds__(HNT, (BF && MODE == 2 && RT == 2 && !QD) ? 2 : 3) v
   publish_max(0, 0);
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
-  int s_run = next_scale(0, kSplitScaleNone);
+  int s_run = split_next_scale<BF>(xmax, 0, kSplitScaleNone);
   split_and_write(ldexpf(1.f, s_run));
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
@@ -505,7 +467,7 @@ __global__ __launch_bounds__(HNT, (BF && MODE == 2 && RT == 2 && !QD) ? 2 : 3) v
       woff += wsize;
     }
     if (vc + 1 < NV) {
-      const int s_next = next_scale((vc + 1) & 1, s_run);
+      const int s_next = split_next_scale<BF>(xmax, (vc + 1) & 1, s_run);
       // sign alternation + rescale, see sr3d_hconv.hip: the sign turns every 2^S2FLIP_SH chunks (a chunk here is short: 12 .. 96
       // MFMAs per wave against 32 packed multiplies for the 64 accumulator registers), and the multiply is skipped when
       // there is neither a turn nor a new scale
@@ -528,13 +490,7 @@ __global__ __launch_bounds__(HNT, (BF && MODE == 2 && RT == 2 && !QD) ? 2 : 3) v
     if (MODE == 1) cls = kcls_n;
   }
 
-  if (export_max && lane == 0) {   // (bits of a non-negative float order like unsigned integers)
-    unsigned* slot = p.amax_out + ((v / p.nblk) & 63);
-    if (rmax0 > 0.f) atomicMax(slot, __float_as_uint(rmax0));
-    if (rmax1 > 0.f) atomicMax(slot + 64, __float_as_uint(rmax1));
-    if (rmax2 > 0.f) atomicMax(slot + 128, __float_as_uint(rmax2));
-    if (rmax3 > 0.f) atomicMax(slot + 192, __float_as_uint(rmax3));
-  }
+  if (export_max && lane == 0) rmax.export_to(p.amax_out + ((v / p.nblk) & 63));
   // ------------------------------------------------------------------ epilogue
   const float out_mult = ldexpf((!BF && (((NV - 1) >> S2FLIP_SH) & 1)) ? -1.f : 1.f, -((s_run == kSplitScaleNone ? 0 : s_run) + sw));
   s2_epilogue<RT, MODE, BF>(p, acc, out_mult, wave, lane, b, nblk, ocls, z0, y0, x0, TZ, TY, TX);
@@ -581,27 +537,17 @@ __global__ __launch_bounds__(HNT, BF ? S2F_WGS_BF : 2) void hconv_s2_fwd_kernel(
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   __builtin_assume(wave >= 0 && wave < HNT / 64);
-  int v;
-  {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
-  const int nblk = v % p.nblk;
-  int blk = v / p.nblk;
-  const int tix = blk % p.ntx;
-  blk /= p.ntx;
-  const int tiy = blk % p.nty;
-  const int tiz = blk / p.nty;
+  const int v = sr3d_xcd_remap(gridDim.x, blockIdx.x);
+  const SplitTile tile = split_tile_of(v, p.nblk, p.ntx, p.nty);
+  const int nblk = tile.nblk;
   const int b = blockIdx.y;
   const int TZ = p.Z, TY = p.Y, TX = p.X;
-  const int z0 = tiz * 2, y0 = tiy * 4, x0 = tix * 32;
+  const int z0 = tile.tiz * 2, y0 = tile.tiy * 4, x0 = tile.tix * 32;
   if (z0 >= TZ || y0 >= TY || x0 >= TX) return;
   const long long IZYX = (long long)p.IZ * p.IY * p.IX;
   const int chan_bytes = (int)(IZYX * ESZ);
 
-  int sw = BF ? 0 : split_scale_exp(*p.absmax_w);
-  if (sw == kSplitScaleNone) sw = 0;
+  const int sw = BF ? 0 : split_scale_exp_or0(*p.absmax_w);
   float* xmax = reinterpret_cast<float*>(Hs + HVOX * 16);
 
   // ---- staging geometry: quad q of halo row (hz, hy); fbase = byte offset for (pz, py) = (0, 0), bit pp of fmask = the
@@ -627,22 +573,7 @@ __global__ __launch_bounds__(HNT, BF ? S2F_WGS_BF : 2) void hconv_s2_fwd_kernel(
     fvox[r] = !task ? 0 : (q == 0 ? 8 : 15);                                 // q = 0: only x = 2 x0 - 1 (odd plane, column 0)
   }
 
-#define SR3D_SLICE_BASE(i) (reinterpret_cast<unsigned long long>(p.in.ptr[i]) + (unsigned long long)((long long)b * p.in.bstride[i]) * ESZ)
-  unsigned long long sb0 = SR3D_SLICE_BASE(0), sb1 = SR3D_SLICE_BASE(1), sb2 = SR3D_SLICE_BASE(2), sb3 = SR3D_SLICE_BASE(3);
-#undef SR3D_SLICE_BASE
-  int cb0 = p.in.cbeg[0], cb1 = p.in.cbeg[1], cb2 = p.in.cbeg[2], cb3 = p.in.cbeg[3];
-  split_pin_scalar(sb0), split_pin_scalar(sb1), split_pin_scalar(sb2), split_pin_scalar(sb3);
-  split_pin_scalar(cb0), split_pin_scalar(cb1), split_pin_scalar(cb2), split_pin_scalar(cb3);
-  unsigned long long dsb1 = sb1 - sb0, dsb2 = sb2 - sb1, dsb3 = sb3 - sb2;
-  int dcb1 = cb1 - cb0, dcb2 = cb2 - cb1, dcb3 = cb3 - cb2;
-  split_pin_scalar(dsb1), split_pin_scalar(dsb2), split_pin_scalar(dsb3), split_pin_scalar(dcb1), split_pin_scalar(dcb2), split_pin_scalar(dcb3);
-  auto slice_of = [&](const int gc) { return (gc >= cb1) + (gc >= cb2) + (gc >= cb3); };
-  auto chan_base = [&](const int gc) {
-    const long long m1 = -(long long)(gc >= cb1), m2 = -(long long)(gc >= cb2), m3 = -(long long)(gc >= cb3);
-    const unsigned long long base = sb0 + (dsb1 & (unsigned long long)m1) + (dsb2 & (unsigned long long)m2) + (dsb3 & (unsigned long long)m3);
-    const int c0 = cb0 + (dcb1 & (int)m1) + (dcb2 & (int)m2) + (dcb3 & (int)m3);
-    return base + (unsigned long long)(unsigned)(gc - c0) * (unsigned long long)(unsigned)chan_bytes;
-  };
+  const SplitSliceBases<ESZ> sl(p.in, b, chan_bytes);   // per-slice base pointers of this sample
 
   const int cpc = p.nchunks;
   const int NV = 4 * cpc;                     // virtual chunk = pair * cpc + 16-channel chunk
@@ -673,41 +604,33 @@ __global__ __launch_bounds__(HNT, BF ? S2F_WGS_BF : 2) void hconv_s2_fwd_kernel(
       }
     };
     const int first = g0 < p.K ? g0 : p.K - 1, last = g0 + 7 < p.K ? g0 + 7 : p.K - 1;
-    if (__builtin_expect(slice_of(first) == slice_of(last), 1)) {
-      unsigned long long base = chan_base(first);
+    if (__builtin_expect(sl.slice_of(first) == sl.slice_of(last), 1)) {
+      unsigned long long base = sl.chan_base(first);
       split_pin_scalar(base);
 #pragma unroll
       for (int c = 0; c < 8; c++) loads(c, base + (unsigned long long)c * (unsigned)chan_bytes);
     } else {
 #pragma unroll
-      for (int c = 0; c < 8; c++) loads(c, chan_base(g0 + c < p.K ? g0 + c : p.K - 1));
+      for (int c = 0; c < 8; c++) loads(c, sl.chan_base(g0 + c < p.K ? g0 + c : p.K - 1));
     }
   };
   // maxima: as in the class form (the pairs together see every element; a quad's columns beyond the halo belong to the same
   // tensor, so the tile scale is only more cautious and the exported maxima stay exact)
   const bool export_max = !BF && p.amax_out != nullptr && nblk == 0;
-  float rmax0 = 0.f, rmax1 = 0.f, rmax2 = 0.f, rmax3 = 0.f;
+  SplitSliceMax rmax;
   auto publish_max = [&](const int parity, const int cc) {
-    if constexpr (BF) return;
     float m = 0.f;
 #pragma unroll
     for (int r = 0; r < FNR; r++)
 #pragma unroll
       for (int c = 0; c < RW; c += 2) m = fmaxf(fmaxf(m, fabsf(raw[r][c])), fabsf(raw[r][c + 1]));
-    m = split_wave_max(m);
-    if (lane == 0) xmax[parity * 4 + wave] = m;
+    m = split_publish_max<BF>(xmax, parity, wave, lane, m);
     if (export_max) {
       const int gc0 = cc * HKC + sh * 8;
-      const int sa = slice_of(gc0 < p.K ? gc0 : p.K - 1), sb = slice_of(gc0 + 7 < p.K ? gc0 + 7 : p.K - 1);
-      auto credit = [&](const int sl, const float mv) {
-        rmax0 = sl == 0 ? fmaxf(rmax0, mv) : rmax0;
-        rmax1 = sl == 1 ? fmaxf(rmax1, mv) : rmax1;
-        rmax2 = sl == 2 ? fmaxf(rmax2, mv) : rmax2;
-        rmax3 = sl == 3 ? fmaxf(rmax3, mv) : rmax3;
-      };
-      if (sa == sb) {
-        credit(sa, m);
-      } else {
+      const int sa = sl.slice_of(gc0 < p.K ? gc0 : p.K - 1), sb = sl.slice_of(gc0 + 7 < p.K ? gc0 + 7 : p.K - 1);
+      int sl_last = sa;
+      float m_last = m;   // one slice: the wave's maximum is that slice's
+      if (sa != sb) {     // the 8 channels straddle a slice boundary (rare: once or twice per layer): one maximum per channel
 #pragma unroll
         for (int c = 0; c < 8; c++) {
           float mc = 0.f;
@@ -716,16 +639,12 @@ __global__ __launch_bounds__(HNT, BF ? S2F_WGS_BF : 2) void hconv_s2_fwd_kernel(
 #pragma unroll
             for (int vx = 0; vx < 4; vx++) mc = fmaxf(mc, fabsf(raw[r][c * 4 + vx]));
           mc = split_wave_max(mc);
-          credit(slice_of(gc0 + c < p.K ? gc0 + c : p.K - 1), mc);
+          const int sc = sl.slice_of(gc0 + c < p.K ? gc0 + c : p.K - 1);
+          if (c < 7) rmax.credit(sc, mc); else sl_last = sc, m_last = mc;
         }
       }
+      rmax.credit(sl_last, m_last);   // (one credit site for both cases, see sr3d_hconv.hip)
     }
-  };
-  auto next_scale = [&](const int parity, const int s_run) {
-    if constexpr (BF) return 0;
-    const float m = fmaxf(fmaxf(xmax[parity * 4 + 0], xmax[parity * 4 + 1]), fmaxf(xmax[parity * 4 + 2], xmax[parity * 4 + 3]));
-    const int s_c = __builtin_amdgcn_readfirstlane(split_scale_exp(m));
-    return s_c < s_run ? s_c : s_run;
   };
   // voxel vx of a quad: x parity vx & 1 -> plane set, halo column 2 q - 1 + (vx >> 1); a 16-byte piece = this wave's 8 channels
   auto split_and_write = [&](const float in_mult) {
@@ -799,7 +718,7 @@ __global__ __launch_bounds__(HNT, BF ? S2F_WGS_BF : 2) void hconv_s2_fwd_kernel(
   publish_max(0, 0);
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
-  int s_run = next_scale(0, kSplitScaleNone);
+  int s_run = split_next_scale<BF>(xmax, 0, kSplitScaleNone);
   split_and_write(ldexpf(1.f, s_run));
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
@@ -900,7 +819,7 @@ __global__ __launch_bounds__(HNT, BF ? S2F_WGS_BF : 2) void hconv_s2_fwd_kernel(
     }
     cbase += T * PIECE;
     if (vc + 1 < NV) {
-      const int s_next = next_scale((vc + 1) & 1, s_run);
+      const int s_next = split_next_scale<BF>(xmax, (vc + 1) & 1, s_run);
       const bool turn = (((vc + 1) >> S2FLIP_SH) ^ (vc >> S2FLIP_SH)) & 1;
       if (!BF && (turn || s_next != s_run)) {
         const float flip = ldexpf(turn ? -1.f : 1.f, s_next - s_run);
@@ -920,13 +839,7 @@ __global__ __launch_bounds__(HNT, BF ? S2F_WGS_BF : 2) void hconv_s2_fwd_kernel(
     pp = pp_n;
   }
 
-  if (export_max && lane == 0) {
-    unsigned* slot = p.amax_out + ((v / p.nblk) & 63);
-    if (rmax0 > 0.f) atomicMax(slot, __float_as_uint(rmax0));
-    if (rmax1 > 0.f) atomicMax(slot + 64, __float_as_uint(rmax1));
-    if (rmax2 > 0.f) atomicMax(slot + 128, __float_as_uint(rmax2));
-    if (rmax3 > 0.f) atomicMax(slot + 192, __float_as_uint(rmax3));
-  }
+  if (export_max && lane == 0) rmax.export_to(p.amax_out + ((v / p.nblk) & 63));
   const float out_mult = ldexpf((!BF && (((NV - 1) >> S2FLIP_SH) & 1)) ? -1.f : 1.f, -((s_run == kSplitScaleNone ? 0 : s_run) + sw));
   s2_epilogue<RT, 1, BF>(p, acc, out_mult, wave, lane, b, nblk, 0, z0, y0, x0, TZ, TY, TX);
 }
@@ -965,30 +878,20 @@ __global__ __launch_bounds__(HNT, 2) void hconv_s2_bwd_pair_kernel(const SrHconv
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   __builtin_assume(wave >= 0 && wave < HNT / 64);
-  int v;
-  {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
-  const int nblk = v % p.nblk;
-  int blk = v / p.nblk;
-  const int tix = blk % p.ntx;
-  blk /= p.ntx;
-  const int tiy = blk % p.nty;
-  const int tiz = blk / p.nty;
+  const int v = sr3d_xcd_remap(gridDim.x, blockIdx.x);
+  const SplitTile tile = split_tile_of(v, p.nblk, p.ntx, p.nty);
+  const int nblk = tile.nblk;
   const int b = blockIdx.y;
   const int pq = (int)blockIdx.z;                 // 2 qz + qy
   const int qz = pq >> 1, qy = pq & 1;
   const int c0 = 4 * qz + 2 * qy;                 // the even-x class of the pair
   const int TZ = p.cZ[c0], TY = p.cY[c0], TX0 = p.cX[c0], TX1 = p.cX[c0 + 1];
-  const int z0 = tiz * 2, y0 = tiy * 4, x0 = tix * 32;
+  const int z0 = tile.tiz * 2, y0 = tile.tiy * 4, x0 = tile.tix * 32;
   if (z0 >= TZ || y0 >= TY || x0 >= TX0) return;  // (the grid is sized for the largest class)
   const long long IZYX = (long long)p.IZ * p.IY * p.IX;
   const int chan_bytes = (int)(IZYX * ESZ);
 
-  int sw = BF ? 0 : split_scale_exp(*p.absmax_w);
-  if (sw == kSplitScaleNone) sw = 0;
+  const int sw = BF ? 0 : split_scale_exp_or0(*p.absmax_w);
   float* xmax = reinterpret_cast<float*>(Hs + HVOX * 16);
 
   unsigned qoff[QNR];
@@ -1006,21 +909,7 @@ __global__ __launch_bounds__(HNT, 2) void hconv_s2_bwd_pair_kernel(const SrHconv
     qmask[r] = !task ? 0 : (q == QPR - 1 ? 1 : 15);
   }
 
-#define SR3D_SLICE_BASE(i) (reinterpret_cast<unsigned long long>(p.in.ptr[i]) + (unsigned long long)((long long)b * p.in.bstride[i]) * ESZ)
-  unsigned long long sb0 = SR3D_SLICE_BASE(0), sb1 = SR3D_SLICE_BASE(1), sb2 = SR3D_SLICE_BASE(2), sb3 = SR3D_SLICE_BASE(3);
-#undef SR3D_SLICE_BASE
-  int cb0 = p.in.cbeg[0], cb1 = p.in.cbeg[1], cb2 = p.in.cbeg[2], cb3 = p.in.cbeg[3];
-  split_pin_scalar(sb0), split_pin_scalar(sb1), split_pin_scalar(sb2), split_pin_scalar(sb3);
-  split_pin_scalar(cb0), split_pin_scalar(cb1), split_pin_scalar(cb2), split_pin_scalar(cb3);
-  unsigned long long dsb1 = sb1 - sb0, dsb2 = sb2 - sb1, dsb3 = sb3 - sb2;
-  int dcb1 = cb1 - cb0, dcb2 = cb2 - cb1, dcb3 = cb3 - cb2;
-  split_pin_scalar(dsb1), split_pin_scalar(dsb2), split_pin_scalar(dsb3), split_pin_scalar(dcb1), split_pin_scalar(dcb2), split_pin_scalar(dcb3);
-  auto chan_base = [&](const int gc) {
-    const long long m1 = -(long long)(gc >= cb1), m2 = -(long long)(gc >= cb2), m3 = -(long long)(gc >= cb3);
-    const unsigned long long base = sb0 + (dsb1 & (unsigned long long)m1) + (dsb2 & (unsigned long long)m2) + (dsb3 & (unsigned long long)m3);
-    const int cc0 = cb0 + (dcb1 & (int)m1) + (dcb2 & (int)m2) + (dcb3 & (int)m3);
-    return base + (unsigned long long)(unsigned)(gc - cc0) * (unsigned long long)(unsigned)chan_bytes;
-  };
+  const SplitSliceBases<ESZ> sl(p.in, b, chan_bytes);   // per-slice base pointers of this sample
 
   const int NV = p.nchunks;
   constexpr int RW = BF ? 8 : 16;    // fp32: [channel 0..3][voxel]; bf16: [channel][dword: voxels (0, 1) | (2, 3)]
@@ -1031,7 +920,7 @@ __global__ __launch_bounds__(HNT, 2) void hconv_s2_bwd_pair_kernel(const SrHconv
 #pragma unroll
     for (int c = 0; c < 4; c++) {
       const int gc = cc * HKC + wave * 4 + c;   // wave-uniform
-      const unsigned long long base = chan_base(gc < p.K ? gc : p.K - 1);
+      const unsigned long long base = sl.chan_base(gc < p.K ? gc : p.K - 1);
       const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, live && gc < p.K ? chan_bytes : 0, 0x00020000);
 #pragma unroll
       for (int r = 0; r < QNR; r++) {
@@ -1048,20 +937,12 @@ __global__ __launch_bounds__(HNT, 2) void hconv_s2_bwd_pair_kernel(const SrHconv
     }
   };
   auto publish_max = [&](const int parity) {
-    if constexpr (BF) return;
     float m = 0.f;
 #pragma unroll
     for (int r = 0; r < QNR; r++)
 #pragma unroll
       for (int c = 0; c < RW; c += 2) m = fmaxf(fmaxf(m, fabsf(rawq[r][c])), fabsf(rawq[r][c + 1]));
-    m = split_wave_max(m);
-    if (lane == 0) xmax[parity * 4 + wave] = m;
-  };
-  auto next_scale = [&](const int parity, const int s_run) {
-    if constexpr (BF) return 0;
-    const float m = fmaxf(fmaxf(xmax[parity * 4 + 0], xmax[parity * 4 + 1]), fmaxf(xmax[parity * 4 + 2], xmax[parity * 4 + 3]));
-    const int s_c = __builtin_amdgcn_readfirstlane(split_scale_exp(m));
-    return s_c < s_run ? s_c : s_run;
+    m = split_publish_max<BF>(xmax, parity, wave, lane, m);
   };
   // channels 4 w .. 4 w + 3 = bytes 8 (w & 1) .. + 7 of the 16-byte piece of channel half w >> 1
   auto split_and_write = [&](const float in_mult) {
@@ -1126,7 +1007,7 @@ __global__ __launch_bounds__(HNT, 2) void hconv_s2_bwd_pair_kernel(const SrHconv
   publish_max(0);
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
-  int s_run = next_scale(0, kSplitScaleNone);
+  int s_run = split_next_scale<BF>(xmax, 0, kSplitScaleNone);
   split_and_write(ldexpf(1.f, s_run));
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
@@ -1193,7 +1074,7 @@ __global__ __launch_bounds__(HNT, 2) void hconv_s2_bwd_pair_kernel(const SrHconv
       woff += ng * GSIZE;
     }
     if (vc + 1 < NV) {
-      const int s_next = next_scale((vc + 1) & 1, s_run);
+      const int s_next = split_next_scale<BF>(xmax, (vc + 1) & 1, s_run);
       const bool turn = (((vc + 1) >> S2FLIP_SH) ^ (vc >> S2FLIP_SH)) & 1;
       if (!BF && (turn || s_next != s_run)) {
         const float flip = ldexpf(turn ? -1.f : 1.f, s_next - s_run);
@@ -1377,12 +1258,6 @@ __global__ __launch_bounds__(256) void hconv_s2_pack_kernel(const S2PackParams p
   }
 }
 
-inline void row_split(int rows, int* n2, int* n1) {
-  const int nfull = rows / 64, rem = rows - nfull * 64;
-  *n2 = nfull + (rem > 32 ? 1 : 0);
-  *n1 = (rem > 0 && rem <= 32) ? 1 : 0;
-}
-
 template <int MODE, bool BF, bool QD = false>
 void launch_rt(int rt, dim3 grid, hipStream_t st, const SrHconvS2Params& p) {
   constexpr size_t lds2 = SGeo<2, BF>::LDS, lds1 = SGeo<1, BF>::LDS;
@@ -1426,7 +1301,7 @@ bool sr3d_hconv_s2_bwd_paired(const SrHconvS2Params& p, bool bf) {
 // header (64 bytes) + region A (64-row blocks) + region B (one block of <= 32 rows); 27 taps per (row block, chunk)
 size_t sr3d_hconv_s2_image_bytes(int rows, int K, bool bf) {
   int n2, n1;
-  row_split(rows, &n2, &n1);
+  split_row_split(rows, &n2, &n1);
   return 64 + (size_t)ceil_div(K, HKC) * 27 * (bf ? 1 : 2) * 1024 * ((size_t)n2 * 2 + (size_t)n1);
 }
 
@@ -1449,7 +1324,7 @@ int sr3d_hconv_s2_pack(int mode, int kind, int Cout, int Cin, int rows, int K, c
   for (int i = 0; i <= SR3D_MAX_SRC; i++) p.rbeg[i] = rbeg ? rbeg[i] : INT_MAX;
   for (int i = 0; i < SR3D_MAX_SRC; i++) p.cbeg[i] = cbeg ? cbeg[i] : 0;
   int n2, n1;
-  row_split(rows, &n2, &n1);
+  split_row_split(rows, &n2, &n1);
   _Float16* body = (_Float16*)((unsigned char*)image + 64);
   for (int region = 0; region < 2; region++) {
     p.nblk = region == 0 ? n2 : n1;
@@ -1472,7 +1347,7 @@ int sr3d_hconv_s2_launch(int mode, SrHconvS2Params& p, const void* image, int B,
   p.absmax_w = (const float*)image;
   p.nchunks = ceil_div(p.K, HKC);
   int n2, n1;
-  row_split(p.N, &n2, &n1);
+  split_row_split(p.N, &n2, &n1);
   static SrPerDevice setup;   // (the attribute is per device, not per thread)
   if (int rc = setup.once([&]() -> int {
         if (int rc2 = set_attrs<false>()) return rc2;

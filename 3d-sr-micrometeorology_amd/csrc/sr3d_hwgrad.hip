@@ -50,12 +50,6 @@ struct WGeo {
   static constexpr int NDY = 32 * RT * 4;              // dY staging items per step (n, 8-voxel piece)
 };
 
-// exponent of the per-tensor scale (0, i.e. no scaling, for an all-zero tensor)
-__host__ __device__ inline int scale_exp_of(float amax) {
-  const int s = split_scale_exp(amax);
-  return s == kSplitScaleNone ? 0 : s;
-}
-
 struct HwParams {
   ChanCat x, dy;
   int cu, N;                 // channels / rows covered
@@ -90,12 +84,7 @@ __global__ __launch_bounds__(WNT) void hwgrad_kernel(const HwParams p) {
   // SAME X and dY rows: they get consecutive virtual ids, and consecutive virtual ids go to ONE XCD (hardware deals
   // block ids round-robin over the 8 XCDs, each with its own L2), so that the group's re-reads are L2 hits of that XCD
   // instead of eight HBM fetches (measured before: 13.8 GB fetched per launch for 2.1 GB of operands).
-  int v;
-  {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    v = p.xcd_order ? (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3) : bid;
-  }
+  int v = p.xcd_order ? sr3d_xcd_remap(gridDim.x, blockIdx.x) : (int)blockIdx.x;
   const int nb = v % p.nnb;
   v /= p.nnb;
   const int cb = v % p.ncb;
@@ -122,7 +111,7 @@ __global__ __launch_bounds__(WNT) void hwgrad_kernel(const HwParams p) {
       const int si = cat_find(p.x, c);
       src = reinterpret_cast<const unsigned char*>(cat_ptr(p.x, si)) + (long long)(c - cat_cbeg(p.x, si)) * ZYX * ESZ;
       src_b = cat_bstride(p.x, si);
-      if constexpr (!BF) mx = ldexpf(1.f, scale_exp_of(p.amax[si]));
+      if constexpr (!BF) mx = ldexpf(1.f, split_scale_exp_or0(p.amax[si]));
       it_on = x0 + 8 * it_q < p.X;
     }
   } else {
@@ -134,7 +123,7 @@ __global__ __launch_bounds__(WNT) void hwgrad_kernel(const HwParams p) {
         const int si = cat_find(p.dy, n);
         src = reinterpret_cast<const unsigned char*>(cat_ptr(p.dy, si)) + (long long)(n - cat_cbeg(p.dy, si)) * ZYX * ESZ;
         src_b = cat_bstride(p.dy, si);
-        if constexpr (!BF) md = ldexpf(1.f, scale_exp_of(p.amax[4 + si]));
+        if constexpr (!BF) md = ldexpf(1.f, split_scale_exp_or0(p.amax[4 + si]));
         it_on = x0 + 8 * it_q < p.X;
       }
     }
@@ -387,6 +376,9 @@ struct HwSliceMap {
 };
 
 // dW[n][c][tap] = 2^-(sx(c)+sd(n)) * sum_s slab[s][tap][n][c]; one thread per output, c fastest (coalesced slab reads)
+// SWAPPED: the kernel's rows n were the layer's INPUT channels and its few channels c the layer's output rows, with the taps
+// mirrored (sr3d_hwgrad_fc): dW[c][n][26 - tap]
+template <bool SWAPPED>
 __global__ __launch_bounds__(256) void hwgrad_reduce_kernel(const float* __restrict__ slab, float* __restrict__ dw, int S, int N,
                                                             int cu, int ldc, int Npad, int Cpad, const float* amax,
                                                             const HwSliceMap sm) {
@@ -397,7 +389,7 @@ __global__ __launch_bounds__(256) void hwgrad_reduce_kernel(const float* __restr
     const long long r = e / cu;
     const int n = (int)(r % N), tap = (int)(r / N);
     const int xi = (c >= sm.xcb[1]) + (c >= sm.xcb[2]) + (c >= sm.xcb[3]), di = (n >= sm.dcb[1]) + (n >= sm.dcb[2]) + (n >= sm.dcb[3]);
-    const float mult = amax ? ldexpf(1.f, -(scale_exp_of(amax[xi]) + scale_exp_of(amax[4 + di]))) : 1.f;   // (bf16: unscaled)
+    const float mult = amax ? ldexpf(1.f, -(split_scale_exp_or0(amax[xi]) + split_scale_exp_or0(amax[4 + di]))) : 1.f;   // (bf16: unscaled)
     const float* s0 = slab + (long long)tap * plane + (long long)n * Cpad + c;
     float s = 0.f;
     int k = 0;
@@ -407,7 +399,10 @@ __global__ __launch_bounds__(256) void hwgrad_reduce_kernel(const float* __restr
       s = (((s + v0) + v1) + v2) + v3;
     }
     for (; k < S; k++) s += s0[(long long)k * 27 * plane];
-    dw[((long long)n * ldc + c) * 27 + tap] = s * mult;
+    if constexpr (SWAPPED)
+      dw[((long long)c * ldc + n) * 27 + (26 - tap)] = s * mult;
+    else
+      dw[((long long)n * ldc + c) * 27 + tap] = s * mult;
   }
 }
 
@@ -423,18 +418,7 @@ HwPlan hw_plan(const sr3d_conv_desc_t* d, int n_total, int c_used) {
   g.Npad = g.nnb * 32 * g.rt, g.Cpad = g.ncb * 32;
   const long long rows = (long long)d->B * d->Z * d->Y;
   const long long cols = (long long)g.nnb * g.ncb * g.nseg;
-  // 2 .. 6 rounds over the 256 CUs (one workgroup per CU), the count that leaves the last round fullest; at least 24
-  // rows per split (4 warm-up steps per plane segment)
-  long long S = 1;
-  double best = -1.0;
-  const long long smax = rows / 24 > 0 ? rows / 24 : 1;
-  const long long s_hi = (1536 + cols - 1) / cols < 96 ? (1536 + cols - 1) / cols : 96;
-  const long long s_lo = (512 + cols - 1) / cols < s_hi ? (512 + cols - 1) / cols : s_hi;
-  for (long long s = s_lo; s <= s_hi; s++) {
-    const long long sc = s < 1 ? 1 : (s > smax ? smax : s);
-    const double wgs = (double)cols * sc, fill = wgs / (256.0 * (double)((long long)(wgs + 255) / 256));
-    if (fill > best + 1e-3) best = fill, S = sc;
-  }
+  const long long S = sr3d_hwgrad_splits(rows, cols, 24);   // (at least 24 rows per split: 4 warm-up steps per plane segment)
   g.rows_per_split = (rows + S - 1) / S;
   g.S = (int)((rows + g.rows_per_split - 1) / g.rows_per_split);
   return g;
@@ -459,6 +443,34 @@ int hw_launch(int rt, long long nwg, const HwParams& p, hipStream_t st) {
 }
 
 }  // namespace
+
+long long sr3d_hwgrad_splits(long long rows, long long cols, int min_rows_per_split) {
+  long long S = 1;
+  double best = -1.0;
+  const long long smax = rows / min_rows_per_split > 0 ? rows / min_rows_per_split : 1;
+  const long long s_hi = (1536 + cols - 1) / cols < 96 ? (1536 + cols - 1) / cols : 96;
+  const long long s_lo = (512 + cols - 1) / cols < s_hi ? (512 + cols - 1) / cols : s_hi;
+  for (long long s = s_lo; s <= s_hi; s++) {
+    const long long sc = s < 1 ? 1 : (s > smax ? smax : s);
+    const double wgs = (double)cols * sc, fill = wgs / (256.0 * (double)((long long)(wgs + 255) / 256));
+    if (fill > best + 1e-3) best = fill, S = sc;
+  }
+  return S;
+}
+
+int sr3d_hwgrad_reduce_launch(const float* slab, float* dw, int S, int N, int C, int ldc, int Npad, int Cpad, const float* amax,
+                              const ChanCat& x, const ChanCat& dy, bool swapped, hipStream_t st) {
+  const long long total = (long long)N * C * 27;
+  const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
+  HwSliceMap sm;
+  for (int i = 0; i < SR3D_MAX_SRC; i++) sm.xcb[i] = x.cbeg[i], sm.dcb[i] = dy.cbeg[i];
+  if (swapped)
+    hipLaunchKernelGGL(hwgrad_reduce_kernel<true>, dim3(blocks), dim3(256), 0, st, slab, dw, S, N, C, ldc, Npad, Cpad, amax, sm);
+  else
+    hipLaunchKernelGGL(hwgrad_reduce_kernel<false>, dim3(blocks), dim3(256), 0, st, slab, dw, S, N, C, ldc, Npad, Cpad, amax, sm);
+  SR3D_HIP(hipGetLastError());
+  return SR3D_OK;
+}
 
 int sr3d_gather_absmax(const unsigned* x_absmax, int nx, const unsigned* dy_absmax, int nd, unsigned* amax, hipStream_t st) {
   hipLaunchKernelGGL(hw_gather_amax_kernel, dim3(1), dim3(64), 0, st, x_absmax, nx, dy_absmax, nd, amax);
@@ -521,12 +533,6 @@ int sr3d_hwgrad(const sr3d_conv_desc_t* d, const ChanCat& x, const ChanCat& dy, 
     if (rc) return rc;
   }
   SrProfScope prof(SR3D_PROF_PACK, 4.0 * ((double)g.S * g.nseg + 1) * 27 * g.Npad * g.Cpad, st);
-  const long long total = (long long)n_total * c_used * 27;
-  const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-  HwSliceMap sm;
-  for (int i = 0; i < SR3D_MAX_SRC; i++) sm.xcb[i] = x.cbeg[i], sm.dcb[i] = dy.cbeg[i];
-  hipLaunchKernelGGL(hwgrad_reduce_kernel, dim3(blocks), dim3(256), 0, st, (const float*)p.slab, dw, g.S * g.nseg, n_total, c_used,
-                     d->Cin, g.Npad, g.Cpad, bf ? (const float*)nullptr : (const float*)amax, sm);
-  SR3D_HIP(hipGetLastError());
-  return SR3D_OK;
+  return sr3d_hwgrad_reduce_launch(p.slab, dw, g.S * g.nseg, n_total, c_used, d->Cin, g.Npad, g.Cpad, bf ? nullptr : (const float*)amax,
+                                   x, dy, false, st);
 }

@@ -50,11 +50,6 @@ __device__ __forceinline__ void fc_static_for(F& f, const int t0, std::integer_s
   (f(std::integral_constant<int, I>{}, t0), ...);
 }
 
-__host__ __device__ inline int fc_scale_exp_of(float amax) {
-  const int s = split_scale_exp(amax);
-  return s == kSplitScaleNone ? 0 : s;
-}
-
 struct FcParams {
   ChanCat x, dy;
   int C, N;                  // channels (<= 5), rows
@@ -100,7 +95,7 @@ __global__ __launch_bounds__(64 * NW, 2) void hwgrad_fc_kernel(const FcParams p)
       const int si = cat_find(p.dy, n);
       d_src = reinterpret_cast<const unsigned char*>(cat_ptr(p.dy, si)) + (long long)(n - cat_cbeg(p.dy, si)) * ZYX * ESZ;
       d_b = cat_bstride(p.dy, si);
-      if constexpr (!BF) md = ldexpf(1.f, fc_scale_exp_of(p.amax[4 + si]));
+      if constexpr (!BF) md = ldexpf(1.f, split_scale_exp_or0(p.amax[4 + si]));
       d_on = x0 + 8 * d_q < p.X;
     }
   }
@@ -115,7 +110,7 @@ __global__ __launch_bounds__(64 * NW, 2) void hwgrad_fc_kernel(const FcParams p)
     const int si = cat_find(p.x, x_c);
     x_src = reinterpret_cast<const unsigned char*>(cat_ptr(p.x, si)) + (long long)(x_c - cat_cbeg(p.x, si)) * ZYX * ESZ;
     x_b = cat_bstride(p.x, si);
-    if constexpr (!BF) mx = ldexpf(1.f, fc_scale_exp_of(p.amax[si]));
+    if constexpr (!BF) mx = ldexpf(1.f, split_scale_exp_or0(p.amax[si]));
     x_on = x0 + 8 * x_q < p.X;
   }
   const int dxq = x0 + 8 * d_q, xxq = x0 + 8 * x_q;
@@ -317,51 +312,6 @@ __global__ __launch_bounds__(64 * NW, 2) void hwgrad_fc_kernel(const FcParams p)
   }
 }
 
-__global__ __launch_bounds__(64) void fc_gather_amax_kernel(const unsigned* xs, int nx, const unsigned* ds, int nd, unsigned* amax) {
-  const int lane = threadIdx.x;
-  for (int i = 0; i < nx + nd; i++) {
-    const unsigned* src = i < nx ? (xs ? xs + i * 64 : nullptr) : (ds ? ds + (i - nx) * 64 : nullptr);
-    if (src == nullptr) continue;
-    float m = __uint_as_float(src[lane]);   // (bits of non-negative floats order like unsigned integers)
-    m = split_wave_max(m);
-    if (lane == 0) amax[i < nx ? i : 4 + (i - nx)] = __float_as_uint(m);
-  }
-}
-
-struct FcSliceMap {
-  int xcb[SR3D_MAX_SRC], dcb[SR3D_MAX_SRC];   // first channel / row of every slice (INT_MAX: unused)
-};
-
-// dW[n][c][tap] = 2^-(sx(c)+sd(n)) * sum_s slab[s][tap][n][c]  (fixed order: deterministic)
-// swapped: the kernel's rows n were the layer's INPUT channels and its few channels c the layer's output rows, with the taps
-// mirrored (sr3d_hwgrad_fc): dW[c][n][26 - tap]
-__global__ __launch_bounds__(256) void hwgrad_fc_reduce_kernel(const float* __restrict__ slab, float* __restrict__ dw, int S, int N, int C,
-                                                               int ldc, int Npad, int Cpad, const float* amax, const FcSliceMap sm,
-                                                               int swapped) {
-  const long long plane = (long long)Npad * Cpad;
-  const long long total = (long long)N * C * 27;
-  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
-    const int c = (int)(e % C);
-    const long long r = e / C;
-    const int n = (int)(r % N), tap = (int)(r / N);
-    const int xi = (c >= sm.xcb[1]) + (c >= sm.xcb[2]) + (c >= sm.xcb[3]), di = (n >= sm.dcb[1]) + (n >= sm.dcb[2]) + (n >= sm.dcb[3]);
-    const float mult = amax ? ldexpf(1.f, -(fc_scale_exp_of(amax[xi]) + fc_scale_exp_of(amax[4 + di]))) : 1.f;   // (bf16: unscaled)
-    const float* s0 = slab + (long long)tap * plane + (long long)n * Cpad + c;
-    float s = 0.f;
-    int k = 0;
-    for (; k + 4 <= S; k += 4) {
-      const float v0 = s0[(long long)k * 27 * plane], v1 = s0[(long long)(k + 1) * 27 * plane];
-      const float v2 = s0[(long long)(k + 2) * 27 * plane], v3 = s0[(long long)(k + 3) * 27 * plane];
-      s = (((s + v0) + v1) + v2) + v3;
-    }
-    for (; k < S; k++) s += s0[(long long)k * 27 * plane];
-    if (swapped)
-      dw[((long long)c * ldc + n) * 27 + (26 - tap)] = s * mult;
-    else
-      dw[((long long)n * ldc + c) * 27 + tap] = s * mult;
-  }
-}
-
 struct FcPlan {
   int nnb, nseg, S, Npad, Cpad;
   long long rows_per_split;
@@ -428,10 +378,8 @@ int sr3d_hwgrad_fc(const sr3d_conv_desc_t* d, const ChanCat& x_real, const ChanC
     if (dy_absmax == nullptr)
       for (int i = 0; i < dy.n; i++)
         if (int rc = sr3d_absmax_launch(dy.ptr[i], (long long)d->B * dy.bstride[i], amax + 4 + i, st)) return rc;
-    if (x_absmax != nullptr || dy_absmax != nullptr) {
-      hipLaunchKernelGGL(fc_gather_amax_kernel, dim3(1), dim3(64), 0, st, x_absmax, x.n, dy_absmax, dy.n, amax);
-      SR3D_HIP(hipGetLastError());
-    }
+    if (x_absmax != nullptr || dy_absmax != nullptr)
+      if (int rc = sr3d_gather_absmax(x_absmax, x.n, dy_absmax, dy.n, amax, st)) return rc;
   }
   static SrPerDevice setup;   // (the attribute is per device, not per thread)
   if (int rc = setup.once([&]() -> int {
@@ -466,12 +414,6 @@ int sr3d_hwgrad_fc(const sr3d_conv_desc_t* d, const ChanCat& x_real, const ChanC
     SR3D_HIP(hipGetLastError());
   }
   SrProfScope prof(SR3D_PROF_PACK, 4.0 * ((double)g.S * g.nseg + 1) * 27 * g.Npad * g.Cpad, st);
-  const long long total = (long long)N * C * 27;
-  const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-  FcSliceMap sm;
-  for (int i = 0; i < SR3D_MAX_SRC; i++) sm.xcb[i] = x.cbeg[i], sm.dcb[i] = dy.cbeg[i];
-  hipLaunchKernelGGL(hwgrad_fc_reduce_kernel, dim3(blocks), dim3(256), 0, st, (const float*)p.slab, dw, g.S * g.nseg, N, C,
-                     d->Cin, g.Npad, g.Cpad, bf ? (const float*)nullptr : (const float*)amax, sm, swapped ? 1 : 0);
-  SR3D_HIP(hipGetLastError());
-  return SR3D_OK;
+  return sr3d_hwgrad_reduce_launch(p.slab, dw, g.S * g.nseg, N, C, d->Cin, g.Npad, g.Cpad, bf ? nullptr : (const float*)amax, x, dy, swapped,
+                                   st);
 }

@@ -49,11 +49,6 @@ struct SGeo {
 };
 static_assert(SGeo<2, false>::LDS <= 160 * 1024, "LDS budget");
 
-__host__ __device__ inline int scale_exp_of(float amax) {
-  const int s = split_scale_exp(amax);
-  return s == kSplitScaleNone ? 0 : s;
-}
-
 struct Hw2Params {
   ChanCat x, dy;
   int cu, N;
@@ -80,12 +75,7 @@ __global__ __launch_bounds__(WNT) void hwgrad_s2_kernel(const Hw2Params p) {
 
   // the nnb x ncb workgroups of one (segment, split) read the SAME X and dY rows: consecutive virtual ids on ONE XCD (its L2), as in
   // sr3d_hwgrad.hip (6.6 GB fetched per launch for 3.1 GB of operands with the plain order, profiles/r04_pmc_hbm_traffic.json)
-  int v;
-  {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  int v = sr3d_xcd_remap(gridDim.x, blockIdx.x);
   const int nb = v % p.nnb;
   v /= p.nnb;
   const int cb = v % p.ncb;
@@ -111,7 +101,7 @@ __global__ __launch_bounds__(WNT) void hwgrad_s2_kernel(const Hw2Params p) {
       const int si = cat_find(p.x, c);
       src = reinterpret_cast<const unsigned char*>(cat_ptr(p.x, si)) + (long long)(c - cat_cbeg(p.x, si)) * IZYX * ESZ;
       src_b = cat_bstride(p.x, si);
-      if constexpr (!BF) mx = ldexpf(1.f, scale_exp_of(p.amax[si]));
+      if constexpr (!BF) mx = ldexpf(1.f, split_scale_exp_or0(p.amax[si]));
       it_on = 2 * x0 + 16 * it_q < p.IX;
     }
   } else {
@@ -123,7 +113,7 @@ __global__ __launch_bounds__(WNT) void hwgrad_s2_kernel(const Hw2Params p) {
         const int si = cat_find(p.dy, n);
         src = reinterpret_cast<const unsigned char*>(cat_ptr(p.dy, si)) + (long long)(n - cat_cbeg(p.dy, si)) * OZYX * ESZ;
         src_b = cat_bstride(p.dy, si);
-        if constexpr (!BF) md = ldexpf(1.f, scale_exp_of(p.amax[4 + si]));
+        if constexpr (!BF) md = ldexpf(1.f, split_scale_exp_or0(p.amax[4 + si]));
         it_on = x0 + 8 * it_q < p.OX;
       }
     }
@@ -330,29 +320,6 @@ __global__ __launch_bounds__(WNT) void hwgrad_s2_kernel(const Hw2Params p) {
     run(std::false_type{});
 }
 
-struct Hw2SliceMap {
-  int xcb[SR3D_MAX_SRC], dcb[SR3D_MAX_SRC];
-};
-
-// dW[n][c][tap] = 2^-(sx(c)+sd(n)) * sum_s slab[s][tap][n][c]  (fixed order: deterministic)
-__global__ __launch_bounds__(256) void hwgrad_s2_reduce_kernel(const float* __restrict__ slab, float* __restrict__ dw, int S, int N,
-                                                               int cu, int ldc, int Npad, int Cpad, const float* amax,
-                                                               const Hw2SliceMap sm) {
-  const long long plane = (long long)Npad * Cpad;
-  const long long total = (long long)N * cu * 27;
-  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
-    const int c = (int)(e % cu);
-    const long long r = e / cu;
-    const int n = (int)(r % N), tap = (int)(r / N);
-    const int xi = (c >= sm.xcb[1]) + (c >= sm.xcb[2]) + (c >= sm.xcb[3]), di = (n >= sm.dcb[1]) + (n >= sm.dcb[2]) + (n >= sm.dcb[3]);
-    const float mult = amax ? ldexpf(1.f, -(scale_exp_of(amax[xi]) + scale_exp_of(amax[4 + di]))) : 1.f;
-    const float* s0 = slab + (long long)tap * plane + (long long)n * Cpad + c;
-    float s = 0.f;
-    for (int k = 0; k < S; k++) s += s0[(long long)k * 27 * plane];
-    dw[((long long)n * ldc + c) * 27 + tap] = s * mult;
-  }
-}
-
 struct Hw2Plan {
   int rt, nnb, ncb, nseg, S, Npad, Cpad, OZ, OY, OX;
   long long rows_per_split;
@@ -366,17 +333,7 @@ Hw2Plan hw2_plan(const sr3d_conv_desc_t* d, int n_total) {
   g.Npad = g.nnb * 32 * g.rt, g.Cpad = g.ncb * CB;
   const long long rows = (long long)d->B * g.OZ * g.OY;
   const long long cols = (long long)g.nnb * g.ncb * g.nseg;
-  // a whole number of rounds over the 256 CUs (one workgroup per CU), at least 16 rows per split (3 warm-up steps)
-  long long S = 1;
-  double best = -1.0;
-  const long long smax = rows / 16 > 0 ? rows / 16 : 1;
-  const long long s_hi = (1536 + cols - 1) / cols < 96 ? (1536 + cols - 1) / cols : 96;
-  const long long s_lo = (512 + cols - 1) / cols < s_hi ? (512 + cols - 1) / cols : s_hi;
-  for (long long s = s_lo; s <= s_hi; s++) {
-    const long long sc = s < 1 ? 1 : (s > smax ? smax : s);
-    const double wgs = (double)cols * sc, fill = wgs / (256.0 * (double)((long long)(wgs + 255) / 256));
-    if (fill > best + 1e-3) best = fill, S = sc;
-  }
+  const long long S = sr3d_hwgrad_splits(rows, cols, 16);   // (at least 16 rows per split: 3 warm-up steps)
   g.rows_per_split = (rows + S - 1) / S;
   g.S = (int)((rows + g.rows_per_split - 1) / g.rows_per_split);
   return g;
@@ -448,12 +405,6 @@ int sr3d_hwgrad_s2(const sr3d_conv_desc_t* d, const ChanCat& x, const ChanCat& d
     if (int rc = bf ? hw2_launch<true>(g.rt, nwg, p, st) : hw2_launch<false>(g.rt, nwg, p, st)) return rc;
   }
   SrProfScope prof(SR3D_PROF_PACK, 4.0 * ((double)g.S * g.nseg + 1) * 27 * g.Npad * g.Cpad, st);
-  const long long total = (long long)n_total * d->Cin * 27;
-  const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-  Hw2SliceMap sm;
-  for (int i = 0; i < SR3D_MAX_SRC; i++) sm.xcb[i] = x.cbeg[i], sm.dcb[i] = dy.cbeg[i];
-  hipLaunchKernelGGL(hwgrad_s2_reduce_kernel, dim3(blocks), dim3(256), 0, st, (const float*)p.slab, dw, g.S * g.nseg, n_total, d->Cin,
-                     d->Cin, g.Npad, g.Cpad, bf ? (const float*)nullptr : (const float*)amax, sm);
-  SR3D_HIP(hipGetLastError());
-  return SR3D_OK;
+  return sr3d_hwgrad_reduce_launch(p.slab, dw, g.S * g.nseg, n_total, d->Cin, d->Cin, g.Npad, g.Cpad, bf ? nullptr : (const float*)amax,
+                                   x, dy, false, st);
 }

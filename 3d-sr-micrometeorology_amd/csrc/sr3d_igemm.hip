@@ -96,12 +96,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const IgemmParams p) {
   // Workgroup -> (row block, tile): the row blocks of one tile read the same input halo, so they should run
   // at the same time on the same XCD (own L2).  Hardware deals blockIdx round-robin over the 8 XCDs, hence
   // ids that are congruent mod 8 are made consecutive in (tile, row block) order (bijective for any grid).
-  int v;
-  {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  int v = sr3d_xcd_remap(gridDim.x, blockIdx.x);
   // launch-wide or per-class (blockIdx.z) description
   int ntaps = p.ntaps, OZ = p.OZ, OY = p.OY, OX = p.OX, pz = p.pz, py = p.py, px = p.px;
   const int* tap_off = p.tap_off;
@@ -330,12 +325,7 @@ __global__ __launch_bounds__(256) void smalln_fwd_kernel(const SmallFwdParams p)
   // neighbouring tiles share halo rows: consecutive tile ids run on ONE XCD (block ids are dealt round-robin over the 8 XCDs, each
   // with its own L2), as in sr3d_hconv.hip -- with the plain order `last`'s forward fetched 11 GB for 2.3 GB of operands
   // (profiles/r04_pmc_hbm_traffic.json) at 5.2 TB/s: it was HBM-bound on its own over-fetch
-  int tile;
-  {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  int tile = sr3d_xcd_remap(gridDim.x, blockIdx.x);
   const int tix = tile % p.ntx;
   tile /= p.ntx;
   const int tiy = tile % p.nty;

@@ -1,4 +1,4 @@
-// Shared pieces of the split-f16 kernels (sr3d_hconv.hip, sr3d_hconv_s2.hip, sr3d_hwgrad.hip): fp32 operands as two fp16
+// Shared pieces of the split-f16 kernels (sr3d_hconv.hip, sr3d_hconv_s2.hip, sr3d_hwgrad.hip, _s2, _fc): fp32 operands as two fp16
 // halves on v_mfma_f32_32x32x16_f16.  gfx950 only.
 #pragma once
 #include "sr3d_common.h"
@@ -28,6 +28,11 @@ __host__ __device__ inline int split_scale_exp(float amax) {
   frexpf(amax, &e);   // amax = m * 2^e, m in [0.5, 1)
   const int s = 14 - e;
   return s > kSplitScaleNone ? kSplitScaleNone : s;
+}
+// ... as the exponent of a per-tensor or per-layer scale: 0, i.e. no scaling, for an all-zero tensor
+__host__ __device__ inline int split_scale_exp_or0(float amax) {
+  const int s = split_scale_exp(amax);
+  return s == kSplitScaleNone ? 0 : s;
 }
 
 // 16 bytes per lane, global -> LDS, buffer form.  (The buffer form on purpose: global_load_lds is a FLAT instruction
@@ -90,6 +95,107 @@ __device__ __forceinline__ float split_wave_max(float m) {
   return fmaxf(fmaxf(r0, r1), fmaxf(r2, r3));
 }
 
+// ---- workgroup geometry shared by the forward / input-gradient kernels (sr3d_hconv.hip, sr3d_hconv_s2.hip)
+// virtual workgroup id -> (row block, voxel tile): the row blocks of one tile run next to each other on one XCD
+struct SplitTile {
+  int nblk, tix, tiy, tiz;
+};
+__device__ __forceinline__ SplitTile split_tile_of(const int v, const int nblk, const int ntx, const int nty) {
+  SplitTile t;
+  t.nblk = v % nblk;
+  int blk = v / nblk;
+  t.tix = blk % ntx;
+  blk /= ntx;
+  t.tiy = blk % nty;
+  t.tiz = blk / nty;
+  return t;
+}
+// GEMM rows -> n2 64-row blocks, and n1 (0 or 1) last block of <= 32 rows
+inline void split_row_split(int rows, int* n2, int* n1) {
+  const int nfull = rows / 64, rem = rows - nfull * 64;
+  *n2 = nfull + (rem > 32 ? 1 : 0);
+  *n1 = (rem > 0 && rem <= 32) ? 1 : 0;
+}
+
+// Per-slice base pointers of sample b of a channel concatenation, pinned in scalar registers: left to itself hipcc turns the
+// slice selects into dependent kernel-argument loads (two or three ~200-cycle scalar-load round trips per channel, in every
+// wave, at the start of every chunk).  ESZ = bytes per element, chan_bytes = bytes of one channel volume.
+// (separate members, not arrays: an array would be indexed in scratch memory)
+template <int ESZ>
+struct SplitSliceBases {
+  unsigned long long sb0, sb1, sb2, sb3, dsb1, dsb2, dsb3;
+  int cb0, cb1, cb2, cb3, dcb1, dcb2, dcb3;
+  int chan_bytes;
+  __device__ __forceinline__ SplitSliceBases(const ChanCat& in, const int b, const int chan_bytes_) : chan_bytes(chan_bytes_) {
+#define SR3D_SLICE_BASE(i) (reinterpret_cast<unsigned long long>(in.ptr[i]) + (unsigned long long)((long long)b * in.bstride[i]) * ESZ)
+    sb0 = SR3D_SLICE_BASE(0), sb1 = SR3D_SLICE_BASE(1), sb2 = SR3D_SLICE_BASE(2), sb3 = SR3D_SLICE_BASE(3);
+#undef SR3D_SLICE_BASE
+    cb0 = in.cbeg[0], cb1 = in.cbeg[1], cb2 = in.cbeg[2], cb3 = in.cbeg[3];
+    split_pin_scalar(sb0), split_pin_scalar(sb1), split_pin_scalar(sb2), split_pin_scalar(sb3);
+    split_pin_scalar(cb0), split_pin_scalar(cb1), split_pin_scalar(cb2), split_pin_scalar(cb3);
+    dsb1 = sb1 - sb0, dsb2 = sb2 - sb1, dsb3 = sb3 - sb2;
+    dcb1 = cb1 - cb0, dcb2 = cb2 - cb1, dcb3 = cb3 - cb2;
+    split_pin_scalar(dsb1), split_pin_scalar(dsb2), split_pin_scalar(dsb3), split_pin_scalar(dcb1), split_pin_scalar(dcb2), split_pin_scalar(dcb3);
+  }
+  __device__ __forceinline__ int slice_of(const int gc) const { return (gc >= cb1) + (gc >= cb2) + (gc >= cb3); }
+  // address of concat channel gc (wave-uniform)
+  // (mask arithmetic instead of selects: hipcc turns a select chain over four values into a lookup table in scratch)
+  __device__ __forceinline__ unsigned long long chan_base(const int gc) const {
+    const long long m1 = -(long long)(gc >= cb1), m2 = -(long long)(gc >= cb2), m3 = -(long long)(gc >= cb3);
+    const unsigned long long base = sb0 + (dsb1 & (unsigned long long)m1) + (dsb2 & (unsigned long long)m2) + (dsb3 & (unsigned long long)m3);
+    const int c0 = cb0 + (dcb1 & (int)m1) + (dcb2 & (int)m2) + (dcb3 & (int)m3);
+    return base + (unsigned long long)(unsigned)(gc - c0) * (unsigned long long)(unsigned)chan_bytes;
+  }
+};
+
+// Running per-slice maxima of |x| over a workgroup's halo tiles, exported at the end for the split-f16 weight gradient of the
+// same layer (it needs max |x| per slice; the forward kernels see every element anyway).
+struct SplitSliceMax {
+  float m0 = 0.f, m1 = 0.f, m2 = 0.f, m3 = 0.f;
+  __device__ __forceinline__ void credit(const int sl, const float mv) {
+    m0 = sl == 0 ? fmaxf(m0, mv) : m0;
+    m1 = sl == 1 ? fmaxf(m1, mv) : m1;
+    m2 = sl == 2 ? fmaxf(m2, mv) : m2;
+    m3 = sl == 3 ? fmaxf(m3, mv) : m3;
+  }
+  // one lane per wave: into slot[slice * 64] (bits of a non-negative float order like unsigned integers)
+  __device__ __forceinline__ void export_to(unsigned* slot) const {
+    if (m0 > 0.f) atomicMax(slot, __float_as_uint(m0));
+    if (m1 > 0.f) atomicMax(slot + 64, __float_as_uint(m1));
+    if (m2 > 0.f) atomicMax(slot + 128, __float_as_uint(m2));
+    if (m3 > 0.f) atomicMax(slot + 192, __float_as_uint(m3));
+  }
+};
+
+// Tile scale: the four waves of a workgroup exchange the largest magnitude of their rows of a chunk through
+// xmax[chunk parity][wave] in LDS (the caller's barrier lies between the two calls).  BF: no scaling, bf16 has fp32's
+// exponent range.
+// this wave's maximum m (one value per lane) -> its slot; returns the maximum, wave-uniform
+template <bool BF>
+__device__ __forceinline__ float split_publish_max(float* xmax, const int parity, const int wave, const int lane, float m) {
+  if constexpr (BF) return 0.f;
+  m = split_wave_max(m);
+  if (lane == 0) xmax[parity * 4 + wave] = m;
+  return m;
+}
+// running scale exponent: the largest chunk magnitude seen so far decides (kSplitScaleNone until a non-zero chunk came)
+template <bool BF>
+__device__ __forceinline__ int split_next_scale(const float* xmax, const int parity, const int s_run) {
+  if constexpr (BF) return 0;
+  const float m = fmaxf(fmaxf(xmax[parity * 4 + 0], xmax[parity * 4 + 1]), fmaxf(xmax[parity * 4 + 2], xmax[parity * 4 + 3]));
+  const int s_c = __builtin_amdgcn_readfirstlane(split_scale_exp(m));
+  return s_c < s_run ? s_c : s_run;
+}
+
 // max |x| of a tensor into *slot with atomicMax (bits of a non-negative float order like unsigned integers; the caller
 // zeroes the slot).  Defined in sr3d_hconv.hip.
 int sr3d_absmax_launch(const float* x, long long n, unsigned* slot, hipStream_t st);
+
+// ---- shared by the weight-gradient files (sr3d_hwgrad.hip, sr3d_hwgrad_s2.hip, sr3d_hwgrad_fc.hip); defined in sr3d_hwgrad.hip
+// Split count of the (b, z, y) rows: 2 .. 6 rounds over the 256 CUs (one workgroup per CU; cols = workgroups per split), the
+// count that leaves the last round fullest, with at least min_rows_per_split rows each (the warm-up steps per plane segment)
+long long sr3d_hwgrad_splits(long long rows, long long cols, int min_rows_per_split);
+// dW[n][c][tap] = 2^-(sx(c)+sd(n)) * sum_s slab[s][tap][n][c], the S slabs summed in a fixed order (amax = nullptr: unscaled);
+// swapped: dW[c][n][26 - tap] (sr3d_hwgrad_fc).  x / dy: the kernel's channel / row operands, for the slice of every c / n.
+int sr3d_hwgrad_reduce_launch(const float* slab, float* dw, int S, int N, int C, int ldc, int Npad, int Cpad, const float* amax,
+                              const ChanCat& x, const ChanCat& dy, bool swapped, hipStream_t st);

@@ -81,12 +81,7 @@ __global__ __launch_bounds__(512, 2) void wino_kernel(const SrWinoParams p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
   // workgroup -> (row block, spatial block); row blocks of one spatial block adjacent on one XCD
-  int v;
-  {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  int v = sr3d_xcd_remap(gridDim.x, blockIdx.x);
   // 64-row block of the layer (index into the packed image) and, for the one-tile variant on small grids, which
   // of its two 32-row tiles this workgroup takes (rt_split: the launch has two workgroups per 64-row block)
   const int rblk = v % p.nblk;

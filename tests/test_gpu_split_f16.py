@@ -266,21 +266,23 @@ def test_unshuffle_layer_accepts_both_row_orders_and_exported_maxima_match_a_swe
     assert relerr(dw_fused, dw_sweep) < 2e-6
 
 
-def test_stride2_forward_exports_exact_slice_maxima(eng, forced):
-    """the stride-2 forward kernel (csrc/sr3d_hconv_s2.hip) exports max|x| per input slice like the stride-1 kernel: exact per
+# (6, 9, 48): X % 4 == 0, the paired forward kernel; (6, 9, 46): X % 4 != 0, the class-form forward with tiles ragged in x
+@pytest.mark.parametrize("grid", [(6, 9, 48), (6, 9, 46)], ids=["x48_paired", "x46_class_form"])
+def test_stride2_forward_exports_exact_slice_maxima(eng, forced, grid):
+    """the stride-2 forward kernels (csrc/sr3d_hconv_s2.hip) export max|x| per input slice like the stride-1 kernel: exact per
     slice although the mask shares an 8-channel staging group with padding, ragged tiles, batch 2"""
     import ctypes as C
     from sr3d_amd import _lib as L
     g = torch.Generator().manual_seed(9)
-    x = ((torch.rand(2, 40, 6, 9, 48, generator=g) - 0.5) * 3.0).to(DEV)
-    m = (torch.rand(2, 1, 6, 9, 48, generator=g) > 0.3).float().to(DEV)
+    x = ((torch.rand(2, 40, *grid, generator=g) - 0.5) * 3.0).to(DEV)
+    m = (torch.rand(2, 1, *grid, generator=g) > 0.3).float().to(DEV)
     wf = (torch.randn(32, 41, 3, 3, 3, generator=g) * 0.05).to(DEV)
     wg = (torch.randn(32, 41, 3, 3, 3, generator=g) * 0.05).to(DEV)
     bg = (torch.randn(32, generator=g) * 0.1).to(DEV)
-    desc = L.conv_desc(2, 41, 32, 6, 9, 48, 2)
+    desc = L.conv_desc(2, 41, 32, *grid, 2)
     assert L.lib.sr3d_conv3d_fwd_exports_absmax(C.byref(desc), 1) == 1
     wp = eng.ops.pack_weights(desc, L.PACK_FWD_GATED, wf, wg)
-    y, ff, ss = (torch.empty(2, 32, 3, 5, 24, device=DEV) for _ in range(3))
+    y, ff, ss = (torch.empty(2, 32, *[(n - 1) // 2 + 1 for n in grid], device=DEV) for _ in range(3))
     xa = torch.zeros(256, dtype=torch.int32, device=DEV)
     L.check(L.lib.sr3d_gated_conv3d_fwd(C.byref(desc), L.slices([x, m]), 2, L.dev_ptr(wp), None, L.dev_ptr(bg), L.dev_ptr(y),
                                         L.dev_ptr(ff), L.dev_ptr(ss), L.ACT_RELU, C.c_void_p(xa.data_ptr()), L.stream_ptr()), "fwd")
