@@ -48,6 +48,13 @@ WALLDIST_SUM_INDEX = {**{{"near": "pos", "near_abs": "pos_abs", "near_sq": "pos_
 WALLDIST_SUM_COUNT = 21
 WALLDIST_MAX_D = 30     # SR3D_WALLDIST_MAX_D
 WALL_DISTANCE_MAX_CAP = 254
+# sr3d_eval_distributions (include/sr3d.h: SR3D_DIST_*): the series (first axis of its outputs), classes and slots
+DIST_SERIES_INDEX = {"ERR_T": 0, "ERR_U": 1, "ERR_V": 2, "ERR_W": 3, "ERR_VEL_NORM": 4, "PRED_T": 5, "PRED_U": 6,
+                     "PRED_V": 7, "PRED_W": 8, "TRUTH_T": 9, "TRUTH_U": 10, "TRUTH_V": 11, "TRUTH_W": 12}
+DIST_SERIES = 13
+DIST_CLASSES = 2        # 0: fluid cells within near_width of a wall, 1: the other fluid cells
+DIST_BINS = 256
+DIST_SLOTS = 259        # underflow, the bins, overflow, NaN
 ROTATE_COEF_READY, ROTATE_PHYSICAL = 1, 2   # flags of the rotation calls (include/sr3d.h: SR3D_ROTATE_*)
 
 
@@ -122,6 +129,9 @@ SYMBOLS = {
     "sr3d_wall_distance": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "sr3d_eval_wall_distance_profiles_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I]),
     "sr3d_eval_wall_distance_profiles": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, C.POINTER(_F), _F, _I, _P, _P, _P, _P]),
+    "sr3d_eval_distributions_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "sr3d_eval_distributions": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), C.POINTER(_F), _I, _I,
+                                     _P, _P, _P, _P, _P]),
     "sr3d_rotate_workspace_bytes":(_SZ, [_I, _I, _I, _I, _I]),
     "sr3d_rotate_fields": (_I, [_P, _P, _I, _I, _I, _I, _I, C.POINTER(_D), C.POINTER(_D), _D, _I, _P, _SZ, _P]),
     "sr3d_rotate_building": (_I, [_P, _P, _I, _I, _I, _I, _I, _D, _D, _I, _P, _SZ, _P]),

@@ -669,6 +669,78 @@ def eval_wall_distance_profiles(p: torch.Tensor, t: torch.Tensor, b: torch.Tenso
     return values, sums
 
 
+def _range_pairs(r, n: int, what: str) -> List[Tuple[float, float]]:
+    """one (lo, hi) pair, or n of them -> n pairs"""
+    r = list(r)
+    if len(r) == 2 and not isinstance(r[0], (list, tuple)):
+        r = [r] * n
+    if len(r) != n or any(len(x) != 2 for x in r):
+        raise ValueError(f"eval_distributions: {what} is one (lo, hi) pair or {n} of them")
+    return [(float(lo), float(hi)) for lo, hi in r]
+
+
+def distribution_ranges(err_range=(-0.5, 0.5), field_range=(-0.5, 1.5), vel_norm_range=(0.0, 8.0)
+                        ) -> Tuple[List[float], List[float]]:
+    """(lo, hi): the bounds of the DIST_SERIES series in the order of ``_lib.DIST_SERIES_INDEX``.  ``err_range`` (the
+    four ERR_c) and ``field_range`` (PRED_c and TRUTH_c alike) are one pair or one pair per channel."""
+    err, field = _range_pairs(err_range, 4, "err_range"), _range_pairs(field_range, 4, "field_range")
+    pairs = err + _range_pairs(vel_norm_range, 1, "vel_norm_range") + field + field
+    for lo, hi in pairs:
+        if not (lo < hi and abs(lo) != float("inf") and abs(hi) != float("inf")):    # a NaN bound fails lo < hi
+            raise ValueError(f"eval_distributions: a range needs finite lo < hi (got {lo}, {hi})")
+    return [lo for lo, _ in pairs], [hi for _, hi in pairs]
+
+
+def eval_distributions(p: torch.Tensor, t: torch.Tensor, b: torch.Tensor, stds: Sequence[Optional[float]], *,
+                       err_range=(-0.5, 0.5), field_range=(-0.5, 1.5), vel_norm_range=(0.0, 8.0), near_width: int = 1,
+                       dist: Optional[torch.Tensor] = None, per_sample: bool = False
+                       ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Histograms of the signed errors, the velocity-error norm and the predicted and true fields over the fluid
+    cells, near the walls and away from them, from one fused pass (include/sr3d.h: sr3d_eval_distributions): returns
+    ``(counts, minmax, cells)`` on the device.  ``counts`` int64 (DIST_SERIES, DIST_CLASSES, DIST_SLOTS), series indexed
+    with ``_lib.DIST_SERIES_INDEX``, class 0 the fluid cells within ``near_width`` cells of a wall and class 1 the
+    others, slot 0 underflow, 1 .. 256 the bins of the series' range, 257 overflow, 258 NaN; ``minmax`` fp32
+    (DIST_SERIES, DIST_CLASSES, 2): exact min and max of the non-NaN values; ``cells`` int64 (3): built, near, far.
+    With ``per_sample`` all three get a leading batch dimension.  Counts add exactly over batches and ranks
+    (``src/error_distributions.py`` derives quantiles and PDF distances from them).
+
+    The ranges are one (lo, hi) pair or one per channel; the defaults keep 256 / (hi - lo) a power of two, so the
+    binning rule is exact on the rounded difference.  ``dist`` = ``wall_distance(b, cap)`` with ``cap >= near_width``,
+    computed here when not given; ``near_width=0`` makes no near-wall class (every fluid cell is class 1).
+    ``stds`` as in ``eval_level_profiles``.  Nothing is cached: every call launches."""
+    p, t, b = p.detach().contiguous(), t.detach().contiguous(), b.detach().contiguous()
+    if p.dim() != 5 or p.shape[1] != 4 or t.shape != p.shape or tuple(b.shape) != (p.shape[0], 1) + tuple(p.shape[2:]):
+        raise ValueError("eval_distributions expects p, t: (B,4,Z,Y,X) and masks: (B,1,Z,Y,X)")
+    if len(stds) != 4:
+        raise ValueError("eval_distributions expects stds = (std_T, std_u, std_v, std_w)")
+    lo, hi = distribution_ranges(err_range, field_range, vel_norm_range)
+    n = int(near_width)
+    if not 0 <= n <= L.WALL_DISTANCE_MAX_CAP:
+        raise ValueError(f"eval_distributions: near_width must be in 0 .. {L.WALL_DISTANCE_MAX_CAP}")
+    if n == 0:
+        dist = None
+    elif dist is None:
+        dist = wall_distance(b, n)
+    elif dist.dtype != torch.uint8 or dist.shape != b.shape:
+        raise ValueError("eval_distributions expects dist: uint8, shaped like the mask (ops.wall_distance)")
+    else:
+        dist = dist.detach().contiguous()
+    B, _, Z, Y, X = p.shape
+    lead = (B,) if per_sample else ()
+    ws = torch.empty(L.lib.sr3d_eval_distributions_workspace_bytes(B, Z, Y, X) // 4, dtype=torch.int32, device=p.device)
+    counts = _empty(lead + (L.DIST_SERIES, L.DIST_CLASSES, L.DIST_SLOTS), p, torch.int64)
+    minmax = _empty(lead + (L.DIST_SERIES, L.DIST_CLASSES, 2), p)
+    cells = _empty(lead + (3,), p, torch.int64)
+    sc = (C.c_float * 4)(*[1.0 if v is None else float(v) for v in stds])
+    L.check(L.lib.sr3d_eval_distributions(L.dev_ptr(p), L.dev_ptr(t), L.dev_ptr(b), L.dev_ptr(dist, "dist", torch.uint8),
+                                          B, Z, Y, X, sc, (C.c_float * L.DIST_SERIES)(*lo), (C.c_float * L.DIST_SERIES)(*hi),
+                                          n, int(bool(per_sample)), L.dev_ptr(counts, "counts", torch.int64),
+                                          L.dev_ptr(minmax), L.dev_ptr(cells, "cells", torch.int64),
+                                          L.dev_ptr(ws, "workspace", torch.int32), L.stream_ptr()),
+            "sr3d_eval_distributions")
+    return counts, minmax, cells
+
+
 def ssim3d(img1: torch.Tensor, img2: torch.Tensor, mask: torch.Tensor, window: Sequence[float], max_val: float = 1.0,
            eps: float = 1e-7, size_average: bool = True) -> torch.Tensor:
     """masked SSIM3D of the reference (src/ssim.py:52-115) as three separable HIP passes; forward only.

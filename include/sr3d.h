@@ -384,6 +384,56 @@ int sr3d_eval_wall_distance_profiles(const void* p, const void* t, const void* b
                                      int X, const float stds[4], float delta_meter, int D, void* sums_out,
                                      void* values_out, void* workspace, void* stream);
 
+/* ---- error-distribution evaluation (csrc/sr3d_eval_dist.hip) ---------------------- */
+/* Histograms of 13 per-voxel series over the fluid cells (b > 0), split by wall distance, from ONE streaming pass
+ * over p, t (B,4,Z,Y,X; fp32, normalised), b (B,1,Z,Y,X) and dist (uint8, made by sr3d_wall_distance with
+ * cap >= near_width; or NULL).  Counts are integers: they add exactly over batches and ranks, and every quantile and
+ * PDF distance follows from them.
+ * Series: ERR_c = p_c - t_c (signed, normalised); ERR_VEL_NORM = sqrtf((a*a + b*b) + c*c) with a = stds[1] * ERR_U,
+ *   b = stds[2] * ERR_V, c = stds[3] * ERR_W, every product and sum rounded to fp32 (the integrand of
+ *   DiffVelocityVectorNorm); PRED_c = p_c, TRUTH_c = t_c.
+ * Classes: 0 = fluid cells with dist <= near_width (the reference's calc_mask_near_build_wall(b, near_width)), 1 = the
+ *   other fluid cells; dist == NULL: every fluid cell is class 1 and near_width is ignored (else 0 <= near_width <= 254).
+ * Slots: 0 underflow, 1 .. 256 the bins, 257 overflow, 258 NaN.  The binning rule of series s is, by definition,
+ *     inv = (float)(256.0 / ((double)hi[s] - (double)lo[s]))      on the host
+ *     k   = floorf((v - lo[s]) * inv)                             fp32: difference and product each rounded, no fma
+ *   k < 0 or v == -inf: underflow; k >= 256 or v == +inf: overflow; NaN: the NaN slot; else slot 1 + k.  Bins are
+ *   left-closed: bin k holds what the rule sends to k, about [lo + k w, lo + (k + 1) w) with w = (hi - lo) / 256.
+ *   hi <= lo, a non-finite bound or a non-finite inv is SR3D_E_ARG.
+ * Outputs (DEVICE): counts_out int64 (SR3D_DIST_SERIES, SR3D_DIST_CLASSES, SR3D_DIST_SLOTS); minmax_out fp32
+ *   (SR3D_DIST_SERIES, SR3D_DIST_CLASSES, 2): exact min and max of the non-NaN values (+inf / -inf for an empty class);
+ *   cells_out int64 (3): built (not b > 0), near, far cells.  per_sample != 0: each gets a leading B, bit-equal to B
+ *   one-sample calls.  Every word of the outputs, and every word of the workspace that is read, is written by the
+ *   call's own kernels: nothing has to be cleared beforehand and a captured call replays faithfully.  Integer sums and
+ *   min / max in a fixed order, no global atomics: two calls are bit-equal.  p, t, b may be any 4-byte-aligned
+ *   contiguous tensors (16-byte loads are used where every channel plane is 16-byte aligned).  Z*Y*X < 2^31, B <= 65535. */
+enum {
+  SR3D_DIST_ERR_T = 0,
+  SR3D_DIST_ERR_U = 1,
+  SR3D_DIST_ERR_V = 2,
+  SR3D_DIST_ERR_W = 3,
+  SR3D_DIST_ERR_VEL_NORM = 4,
+  SR3D_DIST_PRED_T = 5,
+  SR3D_DIST_PRED_U = 6,
+  SR3D_DIST_PRED_V = 7,
+  SR3D_DIST_PRED_W = 8,
+  SR3D_DIST_TRUTH_T = 9,
+  SR3D_DIST_TRUTH_U = 10,
+  SR3D_DIST_TRUTH_V = 11,
+  SR3D_DIST_TRUTH_W = 12
+};
+#define SR3D_DIST_SERIES 13
+#define SR3D_DIST_CLASSES 2
+#define SR3D_DIST_BINS 256
+#define SR3D_DIST_SLOTS 259
+size_t sr3d_eval_distributions_workspace_bytes(int B, int Z, int Y, int X);
+int sr3d_eval_distributions(const void* p, const void* t, const void* b, const void* dist /* uint8 or NULL */,
+                            int B, int Z, int Y, int X, const float stds[4],
+                            const float lo[SR3D_DIST_SERIES], const float hi[SR3D_DIST_SERIES],
+                            int near_width, int per_sample,
+                            void* counts_out, void* minmax_out, void* cells_out,
+                            void* workspace, void* stream);
+
 /* Rotation about the vertical axis (reference src/equivariance_error_calculator.py): every (y, x) plane of an NCDHW
  * fp32 tensor rotated as scipy.ndimage.rotate(a, angle_deg, axes=(-2, -1), reshape=False) does it -- cubic B-spline
  * (prefilter with the mirror boundary, fp64 coefficients), mode 'constant', cval = 0.  angle_deg is reduced modulo
