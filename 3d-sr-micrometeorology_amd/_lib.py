@@ -55,6 +55,13 @@ DIST_SERIES = 13
 DIST_CLASSES = 2        # 0: fluid cells within near_width of a wall, 1: the other fluid cells
 DIST_BINS = 256
 DIST_SLOTS = 259        # underflow, the bins, overflow, NaN
+# sr3d_eval_scale_statistics (include/sr3d.h: SR3D_SCALE_*): the series and moments (last two axes of its sums)
+SCALE_SERIES_INDEX = {"PRED_T": 0, "PRED_U": 1, "PRED_V": 2, "PRED_W": 3, "TRUTH_T": 4, "TRUTH_U": 5, "TRUTH_V": 6,
+                      "TRUTH_W": 7, "ERR_T": 8, "ERR_U": 9, "ERR_V": 10, "ERR_W": 11}
+SCALE_MOMENT_INDEX = {"D1": 0, "D2": 1, "D3": 2, "D4": 3, "F0": 4, "F1": 5, "FF0": 6, "FF1": 7}
+SCALE_DIRS = ("x", "y", "z")
+SCALE_SERIES, SCALE_MOMENTS = 12, 8
+SCALE_MAX_LAG = 64      # SR3D_SCALE_MAX_LAG
 ROTATE_COEF_READY, ROTATE_PHYSICAL = 1, 2   # flags of the rotation calls (include/sr3d.h: SR3D_ROTATE_*)
 
 
@@ -132,6 +139,8 @@ SYMBOLS = {
     "sr3d_eval_distributions_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
     "sr3d_eval_distributions": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), C.POINTER(_F), _I, _I,
                                      _P, _P, _P, _P, _P]),
+    "sr3d_eval_scale_statistics_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I]),
+    "sr3d_eval_scale_statistics": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "sr3d_rotate_workspace_bytes":(_SZ, [_I, _I, _I, _I, _I]),
     "sr3d_rotate_fields": (_I, [_P, _P, _I, _I, _I, _I, _I, C.POINTER(_D), C.POINTER(_D), _D, _I, _P, _SZ, _P]),
     "sr3d_rotate_building": (_I, [_P, _P, _I, _I, _I, _I, _I, _D, _D, _I, _P, _SZ, _P]),

@@ -741,6 +741,40 @@ def eval_distributions(p: torch.Tensor, t: torch.Tensor, b: torch.Tensor, stds: 
     return counts, minmax, cells
 
 
+def eval_scale_statistics(p: torch.Tensor, t: torch.Tensor, b: torch.Tensor, *, max_lag: int = 32,
+                          unobstructed: bool = False, per_sample: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Two-point moments of the predicted, the true and the error field over the valid fluid pairs (x, x + r e_d) from
+    one fused pass (include/sr3d.h: sr3d_eval_scale_statistics): returns ``(sums, pairs)`` on the device, ``sums`` fp64
+    (Z, 3, max_lag, SCALE_SERIES, SCALE_MOMENTS) -- level of the pair's first cell, direction (``_lib.SCALE_DIRS``), lag
+    r = 1 .. max_lag at index r - 1, series (``_lib.SCALE_SERIES_INDEX``), moment (``_lib.SCALE_MOMENT_INDEX``) -- and
+    ``pairs`` int64 (Z, 3, max_lag), the number of valid pairs.  A pair is valid when both cells are fluid (b > 0);
+    with ``unobstructed`` every cell between them must be fluid too.  The sums are of the NORMALISED fields
+    (``src/scale_statistics.py`` turns them into structure functions and correlations in K and m/s).
+
+    With ``per_sample`` both outputs get a leading batch dimension and row i is bit-equal to the one-sample call;
+    without it they are summed over the batch on the device.  Nothing is cached: every call launches."""
+    p, t, b = p.detach().contiguous(), t.detach().contiguous(), b.detach().contiguous()
+    if p.dim() != 5 or p.shape[1] != 4 or t.shape != p.shape or tuple(b.shape) != (p.shape[0], 1) + tuple(p.shape[2:]):
+        raise ValueError("eval_scale_statistics expects p, t: (B,4,Z,Y,X) and masks: (B,1,Z,Y,X)")
+    R = int(max_lag)
+    if not 1 <= R <= L.SCALE_MAX_LAG:
+        raise ValueError(f"eval_scale_statistics: max_lag must be in 1 .. {L.SCALE_MAX_LAG}")
+    B, _, Z, Y, X = p.shape
+    if B < 1 or min(Z, Y, X) < 1:
+        raise ValueError("eval_scale_statistics: empty tensors")
+    pp, tp, bp = L.dev_ptr(p, "p"), L.dev_ptr(t, "t"), L.dev_ptr(b, "b")
+    ws = torch.empty(L.lib.sr3d_eval_scale_statistics_workspace_bytes(B, Z, Y, X, R), dtype=torch.uint8, device=p.device)
+    sums = _empty((B, Z, len(L.SCALE_DIRS), R, L.SCALE_SERIES, L.SCALE_MOMENTS), p, torch.float64)
+    pairs = _empty((B, Z, len(L.SCALE_DIRS), R), p, torch.int64)
+    L.check(L.lib.sr3d_eval_scale_statistics(pp, tp, bp, B, Z, Y, X, R, int(bool(unobstructed)),
+                                             L.dev_ptr(sums, "sums", torch.float64), L.dev_ptr(pairs, "pairs", torch.int64),
+                                             L.dev_ptr(ws, "workspace", torch.uint8), L.stream_ptr()),
+            "sr3d_eval_scale_statistics")
+    if per_sample:
+        return sums, pairs
+    return sums.sum(dim=0), pairs.sum(dim=0)
+
+
 def ssim3d(img1: torch.Tensor, img2: torch.Tensor, mask: torch.Tensor, window: Sequence[float], max_val: float = 1.0,
            eps: float = 1e-7, size_average: bool = True) -> torch.Tensor:
     """masked SSIM3D of the reference (src/ssim.py:52-115) as three separable HIP passes; forward only.

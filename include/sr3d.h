@@ -434,6 +434,56 @@ int sr3d_eval_distributions(const void* p, const void* t, const void* b, const v
                             void* counts_out, void* minmax_out, void* cells_out,
                             void* workspace, void* stream);
 
+/* ---- scale-resolved evaluation (csrc/sr3d_eval_scale.hip) -------------------------- */
+/* Two-point moments over the valid fluid pairs (x, x + r e_d): the raw sums behind structure functions, increment
+ * skewness and flatness and the two-point correlation of the prediction, the truth and the error, per sample, level,
+ * direction d (0 = x, 1 = y, 2 = z) and lag r = 1 .. R.  The building-aware stand-in for a spectrum.
+ * Inputs: p, t (B,4,Z,Y,X; fp32, normalised), b (B,1,Z,Y,X).  A cell is fluid iff b > 0 (as sr3d_eval_distributions).
+ * Pairs: (x, x + r e_d) is valid iff both cells are inside the volume and fluid; with unobstructed != 0 every cell
+ *   between them along d must be fluid too (pairs through a building are dropped).  The pair belongs to the level z of
+ *   its first cell x (d = z: the lower one).  A lag >= the axis length has no pairs: that is no error.
+ * Series: f = (double)p_c (SR3D_SCALE_PRED_T + c), (double)t_c (SR3D_SCALE_TRUTH_T + c) or e_c = (double)p_c -
+ *   (double)t_c (SR3D_SCALE_ERR_T + c), c = 0 .. 3 (T, u, v, w).
+ * Moments, each summed over the valid pairs, with delta = f(x + r e_d) - f(x) in fp64:
+ *   D1 .. D4 = sum delta, delta^2, delta^3, delta^4;  F0 = sum f(x), F1 = sum f(x + r e_d);  FF0 = sum f(x)^2,
+ *   FF1 = sum f(x + r e_d)^2.  Products and sums are fp64, in the implementation's order; an entry with no pairs is
+ *   exactly 0.  What is not stored follows on the host: sum f f' = (FF0 + FF1 - D2) / 2 and
+ *   sum delta_p delta_t = (D2_pred + D2_truth - D2_err) / 2.
+ * The value of a cell that is part of no valid pair never reaches a sum (it is selected out, not multiplied by 0): a
+ *   NaN in a built cell changes nothing.  A NaN in a fluid cell propagates to the sums the cell belongs to.
+ * Outputs (DEVICE): sums_out fp64 (B, Z, SR3D_SCALE_DIRS, R, SR3D_SCALE_SERIES, SR3D_SCALE_MOMENTS); pairs_out int64
+ *   (B, Z, SR3D_SCALE_DIRS, R): the number of valid pairs.  Sample i of a B-sample call is bit-equal to the one-sample
+ *   call on it.  Every word of both outputs, and every word of the workspace that is read, is written by the call's own
+ *   kernels: nothing has to be cleared beforehand and a captured call replays faithfully.  Fixed reduction order, no
+ *   global atomics: two calls are bit-equal.  p, t, b 4-byte aligned, the outputs 8-byte aligned.
+ * SR3D_E_ARG, before anything is launched: R < 1 or R > SR3D_SCALE_MAX_LAG, a null pointer (the workspace included,
+ *   under either pair rule), a non-positive dimension, Z*Y*X >= 2^31, B > 65535. */
+enum {
+  SR3D_SCALE_PRED_T = 0,     /* PRED_U, V, W follow at 1, 2, 3 */
+  SR3D_SCALE_TRUTH_T = 4,    /* TRUTH_U, V, W at 5, 6, 7 */
+  SR3D_SCALE_ERR_T = 8       /* ERR_U, V, W at 9, 10, 11 */
+};
+enum {
+  SR3D_SCALE_MOMENT_D1 = 0,
+  SR3D_SCALE_MOMENT_D2 = 1,
+  SR3D_SCALE_MOMENT_D3 = 2,
+  SR3D_SCALE_MOMENT_D4 = 3,
+  SR3D_SCALE_MOMENT_F0 = 4,
+  SR3D_SCALE_MOMENT_F1 = 5,
+  SR3D_SCALE_MOMENT_FF0 = 6,
+  SR3D_SCALE_MOMENT_FF1 = 7
+};
+#define SR3D_SCALE_MAX_LAG 64
+#define SR3D_SCALE_SERIES 12
+#define SR3D_SCALE_MOMENTS 8
+#define SR3D_SCALE_DIRS 3
+size_t sr3d_eval_scale_statistics_workspace_bytes(int B, int Z, int Y, int X, int R);
+int sr3d_eval_scale_statistics(const void* p, const void* t, const void* b, int B, int Z, int Y, int X,
+                               int R, int unobstructed,
+                               void* sums_out  /* fp64 (B, Z, 3, R, 12, 8) */,
+                               void* pairs_out /* int64 (B, Z, 3, R) */,
+                               void* workspace, void* stream);
+
 /* Rotation about the vertical axis (reference src/equivariance_error_calculator.py): every (y, x) plane of an NCDHW
  * fp32 tensor rotated as scipy.ndimage.rotate(a, angle_deg, axes=(-2, -1), reshape=False) does it -- cubic B-spline
  * (prefilter with the mirror boundary, fp64 coefficients), mode 'constant', cval = 0.  angle_deg is reduced modulo
